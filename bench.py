@@ -1,7 +1,12 @@
 """Benchmark: unet_resnet50 binary segmentation training, 512x512, batch 16 per GPU, bf16 (HIP path).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N)
+
+A plain run sets up, runs the W warmup steps, times the K steps, writes the last timed step's outputs
+when --dump-outputs is given, and prints the result line.  Everything else described below (the
+`roofline` probe step, `cpu_baseline`, `configs`, `card`, `host_enqueue_ms`) takes runs of its own and
+is measured only with --full; a plain run reports those fields as null / empty.
 
 A step = zero_grad + forward + Lovasz-hinge loss + backward (+ RCCL gradient all-reduce when N>1) +
 fused Adam on one synthetic batch already resident in HBM.  After one eager step and one recording
@@ -20,6 +25,14 @@ box can be told from a code change; every configuration also records its card st
 timed steps and `host_enqueue_ms` (the host's cost of enqueueing one step with the GPU parked, after
 the timed region, N=1), so a host-bound rate can be told from a slow GPU.  `median_gpu_ms_per_step` is the median of per-step HIP-event
 times over the K timed steps.
+
+--dump-outputs DIR writes what the last timed step left with its caller, copied off the GPU before
+anything else runs: `loss.npy` (the step's return value), `bn_buffers.npy` (every floating-point
+buffer, concatenated in registration order), and `params.npy` / `grads.npy` (the updated parameter
+arena and the step's gradient arena, float32; an arena above DUMP_MAX_ELEMS elements is sampled at
+fixed seeded positions, the same positions in both).  Rank 0 writes.  Model, batches and sample
+positions are seeded, so the same arguments give the same inputs in every run and two builds can be
+compared array for array.
 """
 from __future__ import annotations
 
@@ -72,6 +85,13 @@ def parse():
                          "from the host, every kernel every step) after one eager and one recording step")
     ap.add_argument("--ddp-bf16", type=int, default=0,
                     help="N>1: all-reduce bf16 copies of the gradient buckets (half the bytes; opt-in)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's loss, parameters, gradients and BN "
+                         "buffers as DIR/<name>.npy (float32; arenas above DUMP_MAX_ELEMS as a fixed seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the roofline probe step, the CPU "
+                         "baseline, the extra configurations, the card and host probes (each still has its own "
+                         "0/1 switch); off: only warmup + timed steps")
     return ap.parse_args()
 
 
@@ -299,6 +319,36 @@ def host_enqueue_ms(run, dev, gpu_ms, steps=3):
     return round(host, 3), load
 
 
+DUMP_MAX_ELEMS = 1 << 22  # per arena: 16 MiB of float32, so one dump stays well under 64 MB
+
+
+def snapshot_outputs(model, loss):
+    """host copies (float32) of what the step that just ran left with its caller: its loss, the
+    updated parameter arena, its gradient arena and the BN buffers.  An arena larger than
+    DUMP_MAX_ELEMS is gathered at sorted positions drawn once from a fixed seed."""
+    flat, grad = model._flat.detach().reshape(-1), model._flat_grad.detach().reshape(-1)
+    if flat.is_cuda:
+        torch.cuda.synchronize(flat.device)
+    n = flat.numel()
+    if n > DUMP_MAX_ELEMS:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(20240611))[:DUMP_MAX_ELEMS]
+        idx = idx.sort().values.to(flat.device)
+        flat, grad = flat[idx], grad[idx]
+    bufs = [b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+    out = {"loss": loss.detach().reshape(-1), "params": flat, "grads": grad}
+    if bufs:
+        out["bn_buffers"] = torch.cat(bufs)
+    return {k: v.float().cpu().numpy() for k, v in out.items()}
+
+
+def write_outputs(dirname, arrays):
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def build_step(model_name, batch, size, loss_name, dev, rank, world, args):
     """(model, step fn) of one configuration: synthetic batches resident in HBM, fused Adam with the
     per-bucket overlapped update, the RCCL bucket all-reduce when world > 1"""
@@ -447,11 +497,17 @@ def main():
     model, step, run, use_graph, overlap = build_step(args.model, args.batch, args.size, args.loss, dev, rank, world,
                                                       args)
     plan_state = getattr(run, "state", None)
+    # a plain run does only what the headline figure needs; the other legs run under --full
+    do_probe, do_host, do_card = (bool(args.full and v) for v in (args.probe, args.host_probe, args.card_probe))
+    do_extra, do_cpu = bool(args.full and args.extra_configs), bool(args.full and args.cpu_baseline)
     torch.cuda.reset_peak_memory_stats(dev)
     wall, median_ms, gpu_ms, loss, card_mid = timed(run, args.steps, args.warmup, world, dev,
-                                                    sample=lambda: card_state(dev))
+                                                    sample=(lambda: card_state(dev)) if args.full else None)
     peak_gib = torch.cuda.max_memory_allocated(dev) / 2 ** 30  # caching-allocator peak over warmup + timed steps
-    host_ms, host_load = host_enqueue_ms(run, dev, median_ms) if world == 1 and args.host_probe else (None, None)
+    # the last timed step's outputs, taken before any probe runs further steps on the model
+    if args.dump_outputs and rank == 0 and loss is not None:
+        write_outputs(args.dump_outputs, snapshot_outputs(model, loss))
+    host_ms, host_load = host_enqueue_ms(run, dev, median_ms) if world == 1 and do_host else (None, None)
     ms_per_step = 1000.0 * wall / args.steps
     imgs_per_s = args.batch * world * args.steps / wall
     final_loss = float(loss.item())
@@ -460,7 +516,7 @@ def main():
     task = "seg+cls multitask" if multitask else "binary seg"
     workload = f"{args.model} {task} {args.size}x{args.size}, per-GPU batch {args.batch}, {args.loss} + Adam"
     roof = None
-    if args.probe:
+    if do_probe:
         ops.PROBE = []
         step(0)
         torch.cuda.synchronize()
@@ -516,7 +572,7 @@ def main():
     torch.cuda.empty_cache()
 
     configs = {}
-    if args.extra_configs:
+    if do_extra:
         for tag, name, batch, loss_name, dp in EXTRA:
             if world > 1 and not dp:
                 continue
@@ -530,7 +586,7 @@ def main():
                                           sample=(lambda: card_state(dev)) if rank == 0 else None)
             peak2 = torch.cuda.max_memory_allocated(dev) / 2 ** 30
             ips = batch * world * k2 / w2
-            host2 = host_enqueue_ms(run2, dev, med2) if world == 1 and args.host_probe else (None, None)
+            host2 = host_enqueue_ms(run2, dev, med2) if world == 1 and do_host else (None, None)
             configs[tag] = {"workload": f"{name} {args.size}x{args.size}, per-GPU batch {batch}, "
                                         f"{loss_name}{' + ce' if name == 'multitask_unet' else ''} + Adam",
                             "value": round(ips, 2), "unit": "images/s", "steps": k2, "ms_per_step": round(1000.0 * w2 / k2, 3),
@@ -545,11 +601,11 @@ def main():
     card = None
     if rank == 0:
         card = {"during": card_mid, "device": torch.cuda.get_device_name(dev)}
-        if args.card_probe:
+        if do_card:
             card.update(card_probe(dev))
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_baseline:
+    if rank == 0 and world == 1 and do_cpu:
         cpu = cpu_baseline(args.model, args.size, args.cpu_batch)
 
     if rank == 0:

@@ -45,6 +45,39 @@ def test_train_and_val_entrypoints(tmp_path, task, model, loss):
     assert 0.0 <= m["IoU"] <= 1.0
 
 
+def test_bench_plain_run_and_output_dump(tmp_path):
+    """bench.py as a command on a small workload (unet_resnet50, 256x256, batch 2): a plain run times
+    exactly --steps steps, reports ms_per_step consistent with its rate, runs none of the --full legs,
+    and --dump-outputs writes the last timed step's loss / parameters / gradients / BN buffers as
+    finite float32 arrays"""
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--size", "256", "--batch", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert (d["steps"], d["warmup"], d["unit"], d["higher_is_better"], d["dtype"]) == (3, 2, "images/s", True, "bf16")
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(2 * 1000.0 / d["ms_per_step"], rel=1e-2)
+    assert d["step_plan"] is not None  # the timed steps are plan replays, as in the flagship run
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["configs"] == {} and d["host_enqueue_ms"] is None
+    arrays = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert sorted(arrays) == ["bn_buffers", "grads", "loss", "params"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+    assert arrays["loss"][0] == pytest.approx(d["final_loss"], abs=1e-5)
+    import bench
+    assert arrays["params"].shape == arrays["grads"].shape == (bench.DUMP_MAX_ELEMS,)  # a sampled arena
+    assert np.abs(arrays["grads"]).max() > 0
+
+
 def test_miou_parity_unet_resnet50_512():
     from model.model_factory import build_model
     from oracle import ref_cpu

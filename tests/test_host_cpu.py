@@ -65,6 +65,50 @@ def test_train_refuses_cpu_and_real_data():
         train.train(train.parse_args(["--device", "cpu", "--epochs", "1"]))
 
 
+def test_bench_cli_plain_run_is_lean(monkeypatch):
+    """bench.py: --full is off by default and --dump-outputs unset; the per-leg switches keep their
+    defaults, so `--full` alone runs every leg"""
+    import bench
+
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.gpus, a.steps, a.warmup, a.full, a.dump_outputs) == (1, 7, 2, False, None)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs) == (True, "d")
+    assert (a.cpu_baseline, a.probe, a.extra_configs, a.card_probe, a.host_probe) == (1, 1, 1, 1, 1)
+
+
+def test_bench_output_dump_is_a_fixed_float32_sample(tmp_path, monkeypatch):
+    """bench.snapshot_outputs / write_outputs on a stand-in model: float32 .npy files; an arena above
+    DUMP_MAX_ELEMS is gathered at the same sorted positions for parameters and gradients, and at the
+    same positions on every call"""
+    import numpy as np
+
+    import bench
+
+    class Stub(torch.nn.Module):
+        def __init__(self, n):
+            super().__init__()
+            self.bn = torch.nn.BatchNorm2d(3)  # running_mean, running_var (float) + num_batches_tracked (int)
+            self._flat = torch.arange(n, dtype=torch.float32)
+            self._flat_grad = -torch.arange(n, dtype=torch.float32)
+
+    m = Stub(1000)
+    a = bench.snapshot_outputs(m, torch.tensor(0.25))
+    assert sorted(a) == ["bn_buffers", "grads", "loss", "params"]
+    assert a["loss"].tolist() == [0.25] and a["bn_buffers"].tolist() == [0, 0, 0, 1, 1, 1]
+    assert np.array_equal(a["params"], np.arange(1000)) and np.array_equal(a["grads"], -a["params"])
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 64)
+    b, c = bench.snapshot_outputs(m, torch.tensor(0.25)), bench.snapshot_outputs(m, torch.tensor(0.25))
+    assert b["params"].shape == (64,) and np.all(np.diff(b["params"]) > 0)
+    assert np.array_equal(b["grads"], -b["params"]) and np.array_equal(b["params"], c["params"])
+    bench.write_outputs(str(tmp_path / "out"), b)
+    for name, arr in b.items():
+        back = np.load(tmp_path / "out" / f"{name}.npy")
+        assert back.dtype == np.float32 and np.array_equal(back, arr)
+
+
 def test_binary_epoch_empty_loader_returns_zero(capsys):
     """an empty train loader returns 0 like the reference (utils/train_and_eval.py:
     185-263 divides by max(seen, 1)) instead of reading the image size of a batch that never came"""

@@ -5,7 +5,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 ex=0
-[ -n "$EXTRA" ] && ex=1
+[ -n "$EXTRA" ] && ex="1 --full"  # the extra configurations are timed only in a --full run
 for i in $(seq 1 ${NB:-3}); do
   k=0
   for v in "$@"; do

@@ -14,7 +14,8 @@ if [ "$MODEL" = multitask_unet ]; then TASK="seg+cls multitask"; else TASK="bina
 WL="$MODEL $TASK 512x512, per-GPU batch $BATCH, $LOSS + Adam"
 B="--model $MODEL --batch $BATCH --loss $LOSS"
 # the C2 line carries the extra configurations (C4, C5); a C4 / C5 run times its own model only
-if [ "$MODEL" = unet_resnet50 ]; then XB=""; else XB="--extra-configs 0 --cpu-baseline 0"; fi
+# (--full: the bench line kept in profiles/ carries the roofline, card, host and CPU-baseline legs)
+if [ "$MODEL" = unet_resnet50 ]; then XB="--full"; else XB="--full --extra-configs 0 --cpu-baseline 0"; fi
 timeout -k 10 400 python bench.py $B $XB > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || { echo bench failed; tail gpurun_out/${TAG}_bench.err; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_prof -o run -- python bench.py $B --steps 5 --warmup 2 --cpu-baseline 0 --extra-configs 0 --card-probe 0 --host-probe 0 --probe 0 > gpurun_out/${TAG}_prof.log 2>&1 || { echo prof failed; exit 1; }
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/${TAG}_pmcF -o run -- python bench.py $B --steps 2 --warmup 1 --cpu-baseline 0 --probe 0 --extra-configs 0 --card-probe 0 --host-probe 0 > gpurun_out/${TAG}_pmcF.log 2>&1 || { echo pmc fetch failed; exit 1; }
