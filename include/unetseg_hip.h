@@ -368,6 +368,26 @@ int unetseg_mc_confusion(const float* out, const int64_t* tgt, int B, int C, lon
 int unetseg_softmax_resize_argmax(const float* logits, int C, int H, int W, int y0, int x0, int ch, int cw, int OH,
                                   int OW, int32_t* labels, void* stream);
 
+/* ---- tiled full-resolution inference (no reference counterpart; predict.predict_labels_tiled) ------
+ * Grid (utils/tiling.py): tile t, overlap o (0 <= o <= t / 2), stride s = t - o,
+ * n = max(1, ceil((L - o) / s)) tiles per axis at origins i * s (they may hang over the far edge),
+ * row-major tile index iy * nx + ix.  Window w(u) = min(1, (u + 1) / (o + 1), (t - u) / (o + 1)) in fp32;
+ * blended probability = sum_i w_i softmax(logits_i) / sum_i w_i over the (at most 4) covering tiles in
+ * ascending index.  2 <= C <= 32.  Tile ranges t0 .. t0+nt-1 may be issued in any split, in ascending
+ * order on one stream: the accumulated bits do not depend on the split. */
+/* host only: tiles per row (nx) and per column (ny) */
+int unetseg_tile_count(int H, int W, int tile, int overlap, int* nx, int* ny);
+/* out fp32 [nt][3][tile][tile] = img (uint8 HWC RGB, device) / 255, fill / 255 outside the image */
+int unetseg_tile_gather(const uint8_t* img, int H, int W, int tile, int overlap, int t0, int nt, int fill,
+                        float* out, void* stream);
+/* acc fp32 [C][H][W] (zeroed by the caller) += window * softmax over C of logits fp32 [nt][C][tile][tile] */
+int unetseg_tile_accum(const float* logits, int C, int H, int W, int tile, int overlap, int t0, int nt, float* acc,
+                       void* stream);
+/* probs fp32 [C][H][W] (may be NULL) = acc / total window weight; labels int32 [H][W] = argmax (a tie
+ * goes to the lowest class) */
+int unetseg_tile_finish(const float* acc, int C, int H, int W, int tile, int overlap, float* probs, int32_t* labels,
+                        void* stream);
+
 /* ---- device augmentation of the loader (utils/hf_dataloader.py:67-105, 111-180, 183-213) -------
  * Replaces HFUnetDataset.get_random_data + preprocess + hf_unet_dataset_collate for one batch:
  * PIL BICUBIC image / NEAREST mask resize (bit-exact), flip, paste on the grey / zero canvas,

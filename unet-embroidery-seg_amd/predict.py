@@ -10,6 +10,11 @@ every byte value), the model on the HIP kernels, and softmax + crop + resize + a
 edge clamp) and blends with cv2.addWeighted; cv2 is absent here, so the label map follows that
 published rule (parity unpinned, see tests/test_gpu_predict.py) and the blend is
 round-half-even of 0.3 a + 0.7 b in float32.
+
+``--tile T`` (no reference counterpart) runs the model over the image at its native resolution
+instead: overlapping T x T tiles cut on the device, batched eval-mode forwards, and the per-tile
+class probabilities blended back into one map (csrc/tiles.hip, utils/tiling.py).  The default,
+``--tile 0``, is the letterbox path above, unchanged.
 """
 from __future__ import annotations
 
@@ -30,10 +35,12 @@ from PIL import Image  # noqa: E402
 
 from model.model_factory import SUPPORTED_MODELS, build_model  # noqa: E402
 from unetseg_hip.lib import lib  # noqa: E402
+from utils import tiling  # noqa: E402
 from utils.hf_dataloader import RawSample, pack_batch  # noqa: E402
 from utils.utils import cvtColor, letterbox_params  # noqa: E402
 
 INPUT_SHAPE = (480, 480)  # predict.py:55
+TILE_FILL = 128  # outside the image a tile shows the letterbox canvas grey the models were trained against
 VOC_COLORS = [(0, 0, 0), (128, 0, 0), (0, 128, 0), (128, 128, 0), (0, 0, 128), (128, 0, 128), (0, 128, 128),
               (128, 128, 128), (64, 0, 0), (192, 0, 0), (64, 128, 0), (192, 128, 0), (64, 0, 128), (192, 0, 128),
               (64, 128, 128), (192, 128, 128), (0, 64, 0), (128, 64, 0), (0, 192, 0), (128, 192, 0), (0, 64, 128),
@@ -87,6 +94,59 @@ def predict_labels(model, image, device):
     return labels.cpu().numpy()
 
 
+def predict_labels_tiled(model, image, device, tile=512, overlap=64, tile_batch=8, bf16=False, return_probs=False):
+    """the argmax label map int32 [H][W] of the image at its native resolution: overlapping tiles
+    (utils/tiling.py) gathered on the device, ``model`` (any callable [B,3,t,t] fp32 -> [B,C,t,t]
+    logits, C >= 2) run over ranges of ``tile_batch`` tiles, the window-weighted softmax of every tile
+    accumulated in ascending tile order and normalised.  With ``return_probs`` also the blended fp32
+    probabilities [C][H][W]."""
+    tiling.check(tile, overlap)
+    rgb = np.array(image, np.uint8)  # a writable C-contiguous copy (a PIL image's buffer is read-only)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"expected an RGB image [H][W][3], got shape {rgb.shape}")
+    H, W = rgb.shape[:2]
+    nx, ny = tiling.grid(H, W, tile, overlap)
+    img = torch.from_numpy(rgb).to(device)
+    st = torch.cuda.current_stream(device).cuda_stream
+    acc = None
+    for t0, nt in tiling.ranges(nx * ny, tile_batch):
+        x = torch.empty(nt, 3, tile, tile, dtype=torch.float32, device=device)
+        lib.tile_gather(img.data_ptr(), H, W, tile, overlap, t0, nt, TILE_FILL, x.data_ptr(), st)
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=bf16):
+            lg = model(x)
+        if lg.dim() != 4 or lg.shape[0] != nt or tuple(lg.shape[2:]) != (tile, tile):
+            raise ValueError(f"the model returned {tuple(lg.shape)} for {nt} tiles of {tile}")
+        C = lg.shape[1]
+        if C < 2 or C > 32:
+            raise ValueError(f"tiled inference blends softmax probabilities of 2..32 classes, got C={C}")
+        lg = lg.float().contiguous()
+        if acc is None:
+            acc = torch.zeros(C, H, W, dtype=torch.float32, device=device)
+        elif acc.shape[0] != C:
+            raise ValueError(f"the model returned {C} classes after {acc.shape[0]}")
+        lib.tile_accum(lg.data_ptr(), C, H, W, tile, overlap, t0, nt, acc.data_ptr(), st)
+    labels = torch.empty(H, W, dtype=torch.int32, device=device)
+    probs = torch.empty_like(acc) if return_probs else None
+    lib.tile_finish(acc.data_ptr(), acc.shape[0], H, W, tile, overlap, probs.data_ptr() if return_probs else None,
+                    labels.data_ptr(), st)
+    if return_probs:
+        return labels.cpu().numpy(), probs.cpu().numpy()
+    return labels.cpu().numpy()
+
+
+def check_tiling(tile, overlap, tile_batch=8):
+    """the command line's tiling options: tile 0 = letterbox; else a multiple of 32 (the encoders halve
+    the input five times) with 0 <= overlap <= tile // 2"""
+    if tile == 0:
+        return
+    if tile < 0 or tile % 32:
+        raise ValueError(f"--tile must be 0 (letterbox) or a positive multiple of 32, got {tile}")
+    if overlap < 0 or overlap > tile // 2:
+        raise ValueError(f"--overlap must lie in [0, tile // 2 = {tile // 2}], got {overlap}")
+    if tile_batch <= 0:
+        raise ValueError(f"--tile-batch must be positive, got {tile_batch}")
+
+
 def blend(old, seg, alpha=0.7):
     """cv2.addWeighted(old, 1 - alpha, seg, alpha, 0) for uint8 (float32 arithmetic, round half even)"""
     f = np.float32
@@ -94,8 +154,9 @@ def blend(old, seg, alpha=0.7):
     return np.clip(np.rint(v), 0, 255).astype(np.uint8)
 
 
-def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, device=None):
-    """predict.py:41-109"""
+def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, device=None, tile=0, overlap=64,
+                 tile_batch=8, bf16=False):
+    """predict.py:41-109; tile > 0 takes the label map from predict_labels_tiled"""
     try:
         image = Image.open(file_path)
     except (FileNotFoundError, IOError) as e:
@@ -104,7 +165,10 @@ def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, devic
     device = device or torch.device("cuda")
     image = cvtColor(image)
     old_img = image.copy()
-    pr = predict_labels(model, image, device)
+    if tile:
+        pr = predict_labels_tiled(model, image, device, tile=tile, overlap=overlap, tile_batch=tile_batch, bf16=bf16)
+    else:
+        pr = predict_labels(model, image, device)
     oh, ow = pr.shape
     seg_img = np.reshape(np.array(colors_for(num_classes), np.uint8)[np.reshape(pr, [-1])], [oh, ow, -1])
     out = Image.fromarray(blend(np.array(old_img), seg_img)) if mix_type else Image.fromarray(np.uint8(seg_img))
@@ -128,6 +192,7 @@ def create_val_exp_folder(root="run"):
 
 def predict(args):
     """predict.py:112-145"""
+    check_tiling(args.tile, args.overlap, args.tile_batch)
     exp_folder = create_val_exp_folder(args.out_dir)
     num_classes = args.num_classes + 1
     assert os.path.exists(args.weights), f"weights {args.weights} not found."
@@ -142,7 +207,8 @@ def predict(args):
     else:
         raise ValueError(f"Unsupported input path: {args.data_path}")
     t0 = time_synchronized()
-    saved = [detect_image(f, model, num_classes, exp_folder, mix_type=args.mix_type, device=device)
+    saved = [detect_image(f, model, num_classes, exp_folder, mix_type=args.mix_type, device=device, tile=args.tile,
+                          overlap=args.overlap, tile_batch=args.tile_batch, bf16=args.bf16)
              for f in files if f.endswith((".jpg", ".png", ".jpeg"))]
     print(f"inference time for: {time_synchronized() - t0}")
     return saved
@@ -157,6 +223,11 @@ def parse_args(argv=None):
     p.add_argument("--model", default="unet_resnet50", choices=sorted(SUPPORTED_MODELS.keys()))
     p.add_argument("--mix_type", default=True, action="store_true")
     p.add_argument("--out-dir", default="run")
+    p.add_argument("--tile", default=0, type=int,
+                   help="0: letterbox to 480x480; T > 0 (a multiple of 32): native resolution in T x T tiles")
+    p.add_argument("--overlap", default=64, type=int, help="pixels neighbouring tiles share (<= tile // 2)")
+    p.add_argument("--tile-batch", default=8, type=int, help="tiles per forward")
+    p.add_argument("--bf16", action="store_true", help="tiled path: run the forward under bf16 autocast")
     return p.parse_args(argv)
 
 

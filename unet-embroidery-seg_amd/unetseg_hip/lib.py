@@ -126,6 +126,10 @@ SIGNATURES = {
     "unetseg_augment_batch": (I, [P, P, I, P, P, LL, P, LL, P, LL, P, LL, P, LL, I, I, I, I, P, P, P, P]),
     "unetseg_augment_batch_dev": (I, [P, P, I, P, P, LL, P, LL, P, LL, P, LL, P, LL, I, I, I, I, P, P, P, P]),
     "unetseg_augment_tables_dev": (I, [P, I, P, P, I, P]),
+    "unetseg_tile_count": (I, [I, I, I, I, P, P]),
+    "unetseg_tile_gather": (I, [P, I, I, I, I, I, I, I, P, P]),
+    "unetseg_tile_accum": (I, [P, I, I, I, I, I, I, I, P, P]),
+    "unetseg_tile_finish": (I, [P, I, I, I, I, I, P, P, P]),
 }
 
 #: functions returning a value rather than a status (no RuntimeError on non-zero)
@@ -271,6 +275,13 @@ def wgrad_config(dtype, c1, ldc1, c2, ldc2, n, h, w, ldy, cout, r, s, stride, pa
     kind = load().unetseg_conv2d_wgrad_config(dtype, c1, ldc1, c2, ldc2, n, h, w, ldy, cout, r, s, stride, pad,
                                               ctypes.byref(sp))
     return WG_NAMES.get(kind, str(kind)), sp.value, "reduce"
+
+
+def tile_count(h, w, tile, overlap):
+    """(nx, ny) of the tiled-inference grid (utils/tiling.py's rule, as the library computes it)"""
+    nx, ny = ctypes.c_int(0), ctypes.c_int(0)
+    lib.tile_count(h, w, tile, overlap, ctypes.addressof(nx), ctypes.addressof(ny))
+    return nx.value, ny.value
 
 
 def stem_config(n, h, w, K):
