@@ -343,21 +343,21 @@ def test_upsample_strided_grad(dtname, align, H, C):
     assert _rel(_nchw(xn.grad), xr.grad + g0) < tol
 
 
-@pytest.mark.parametrize("dtname", ["fp32", "bf16"])
-@pytest.mark.parametrize("K", [1, 2])
-@pytest.mark.parametrize("N,H,W", [(2, 37, 50), (1, 64, 64), (3, 5, 7)])
-def test_pw_head(dtname, K, N, H, W):
-    """1x1 head conv (64 -> K, bias) to fp32 NCHW logits, forward and backward"""
+def _pw_head_case(dtname, K, N, H, W, C=64, preload=False, need_grad=True):
+    """1x1 head conv (C -> K, bias) to fp32 NCHW logits, forward and backward.  K in {1, 2} is the
+    pw_small path, K in 3..32 the C-way pw_head kernels of csrc/multiclass.hip (whose backward needs C
+    to divide 256).  preload: the input node already holds a gradient (a second consumer ran first),
+    so dx accumulates (dx_acc = 1); need_grad False: the input takes no gradient (dx NULL)."""
     ops, DT_BF16, DT_F32 = _ops()
     from unetseg_hip.nn import Conv2d
     dt = DT_BF16 if dtname == "bf16" else DT_F32
     g = torch.Generator().manual_seed(13)
-    conv = Conv2d(64, K, 1).to(DEV)
+    conv = Conv2d(C, K, 1).to(DEV)
     conv.weight.grad = torch.zeros_like(conv.weight)
     conv.bias.grad = torch.zeros_like(conv.bias)
-    x = _round(torch.randn(N, 64, H, W, generator=g), dt)
+    x = _round(torch.randn(N, C, H, W, generator=g), dt)
     ctx = _ctx(dt)
-    xn = _node(x, dt)
+    xn = _node(x, dt, need_grad)
     y, holder = ops.pw_head(ctx, xn, conv)
     xr = x.clone().requires_grad_(True)
     wr = conv.weight.detach().cpu().clone().requires_grad_(True)
@@ -367,11 +367,46 @@ def test_pw_head(dtname, K, N, H, W):
     assert _rel(y.cpu(), ref.detach()) < tol
     dy = torch.randn(ref.shape, generator=g)
     holder["grad"] = dy.to(DEV)
+    g0 = torch.zeros_like(x)
+    if preload:
+        g0 = _round(torch.randn(x.shape, generator=g), dt)
+        xn.grad = _node(g0, dt).data.clone()
     ctx.backward()
     ref.backward(dy)
-    assert _rel(_nchw(xn.grad), xr.grad) < tol
+    print(f"PWHEAD {dtname} K{K} C{C} {N}x{H}x{W} preload={preload}: y {_rel(y.cpu(), ref.detach()):.2e} "
+          f"dx {_rel(_nchw(xn.grad), xr.grad + g0) if need_grad else 0.0:.2e} "
+          f"dW {_rel(conv.weight.grad.cpu(), wr.grad):.2e} db {_rel(conv.bias.grad.cpu(), br.grad):.2e}")
+    if need_grad:
+        assert _rel(_nchw(xn.grad), xr.grad + g0) < tol
+    else:
+        assert xn.grad is None
     assert _rel(conv.weight.grad.cpu(), wr.grad) < 1e-4
     assert _rel(conv.bias.grad.cpu(), br.grad) < 1e-4
+
+
+@pytest.mark.parametrize("dtname", ["fp32", "bf16"])
+@pytest.mark.parametrize("K", [1, 2, 3, 21, 32])
+@pytest.mark.parametrize("N,H,W", [(2, 37, 50), (1, 64, 64), (3, 5, 7)])
+def test_pw_head(dtname, K, N, H, W):
+    """1x1 head conv (64 -> K, bias) to fp32 NCHW logits, forward and backward"""
+    _pw_head_case(dtname, K, N, H, W)
+
+
+@pytest.mark.parametrize("dtname", ["fp32", "bf16"])
+@pytest.mark.parametrize("K", [3, 21, 32])
+@pytest.mark.parametrize("C", [32, 256])
+@pytest.mark.parametrize("N,H,W", [(2, 37, 50), (1, 64, 64), (3, 5, 7)])
+def test_pw_head_channels(dtname, K, C, N, H, W):
+    """the C-way head at the other input widths its backward takes (8 / 1 pixel rows per block)"""
+    _pw_head_case(dtname, K, N, H, W, C=C)
+
+
+@pytest.mark.parametrize("dtname", ["fp32", "bf16"])
+@pytest.mark.parametrize("K", [2, 21])
+@pytest.mark.parametrize("mode", ["second_consumer", "no_input_grad"])
+def test_pw_head_dx_modes(dtname, K, mode):
+    """dx accumulated onto an existing gradient (dx_acc = 1) and dx NULL, two pixel tiles"""
+    _pw_head_case(dtname, K, 2, 37, 50, preload=mode == "second_consumer", need_grad=mode != "no_input_grad")
 
 
 @pytest.mark.parametrize("B,H,W", [(3, 40, 48), (2, 64, 64), (1, 7, 5)])

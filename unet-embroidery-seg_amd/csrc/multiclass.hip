@@ -282,7 +282,9 @@ __global__ __launch_bounds__(256) void mc_loss_bwd_kernel(McArgs a, const double
         const float al = a.alpha >= 0.f ? a.alpha : 1.f;
         // L = -al (1-pt)^gm logpt ; dL/dlogpt = al [gm (1-pt)^(gm-1) pt logpt - (1-pt)^gm]
         const float om = 1.f - pt;
-        const float dldl = al * (a.gamma * powf(om, a.gamma - 1.f) * pt * logpt - powf(om, a.gamma));
+        // gm = 0: (1-pt)^0 is constant, its term is 0 (torch's pow backward) -- not 0 * 0^-1 = NaN at pt == 1
+        const float dpow = a.gamma == 0.f ? 0.f : a.gamma * powf(om, a.gamma - 1.f);
+        const float dldl = al * (dpow * pt * logpt - powf(om, a.gamma));
         k = -dldl * wt * inv_n;  // dlogpt/dx_c = -wt (p_c - [c==t])
       }
     }
