@@ -141,6 +141,7 @@ bool wgrad_fast_ok(const FastWgradArgs& a);
 bool wgrad_ring_ok(const FastWgradArgs& a);  // launch_wgrad_fast takes the LDS-DMA ring kernel
 int launch_wgrad_ring(const FastWgradArgs& a, int splits, hipStream_t st);  // conv_wgrad_ring.hip
 int wgrad_fast_splits(int Cout, int Ng, long Kpix);
+int wgrad_fast_kind(const FastWgradArgs& a);  // the kWgFast* / kWgRing* kernel launch_wgrad_fast runs
 int launch_wgrad_fast(FastWgradArgs a, int splits, hipStream_t st);
 
 // the plain / attention U-Nets' first 3x3 conv on the packed image (conv_first.hip): 3 -> 64 channels,

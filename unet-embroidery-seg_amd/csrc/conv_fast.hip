@@ -908,7 +908,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, (tn_waves_per_simd<BM, BN, NWM, NWN
 }
 
 // Several independent GEMMs of one configuration in one launch: the output-parity classes of a
-// stride-2 data gradient (conv.hip dgrad_classes; 4 / 2 / 2 / 1 taps, a few hundred tiles each),
+// stride-2 data gradient (conv.hip plan_dgrad; 4 / 2 / 2 / 1 taps, a few hundred tiles each),
 // which launched one after another left the chip mostly idle.  Blocks [start[k], start[k+1]) run
 // GEMM k as its own gx[k] x gy[k] grid.
 struct TNMulti {
@@ -1989,30 +1989,34 @@ static void launch_wgrad_cfg(const FastWgradArgs& a, int splits, hipStream_t st)
   hipLaunchKernelGGL((wgrad_fast_kernel<BM, BN, NWM, NWN, ROW32, PRE>), grid, dim3(64 * NWM * NWN), lds, st, a);
 }
 
+// Which kernel of the fast family a call runs: the LDS-DMA ring where it applies (wgrad_ring_ok), else
+// the register-staged 64x256 (<= 64 output channels) or 128x128 tile, each with or without ROW32.
+// ROW32: every K step is one 32-pixel run of an output row, and the per-lane pixel deltas and
+// scalar bases fit 32-bit offsets (the caller bounds both tensors below 2^31 bytes)
+int wgrad_fast_kind(const FastWgradArgs& a) {
+  const bool small = a.Cout <= 64;
+  if (wgrad_ring_ok(a)) return small ? kWgRing64x256 : kWgRing128;
+  static const bool no_row = getenv("UNETSEG_WG_NO_ROW32") != nullptr;
+  const bool row32 = !no_row && a.Q % kWgBK == 0;
+  return small ? (row32 ? kWgFastRow64x256 : kWgFast64x256) : (row32 ? kWgFastRow128 : kWgFast128);
+}
+
+template <bool PRE>
+static void launch_wgrad_kind(int kind, const FastWgradArgs& a, int splits, hipStream_t st) {
+  switch (kind) {
+    case kWgFastRow64x256: return launch_wgrad_cfg<64, 256, 1, 4, true, PRE>(a, splits, st);
+    case kWgFast64x256: return launch_wgrad_cfg<64, 256, 1, 4, false, PRE>(a, splits, st);
+    case kWgFastRow128: return launch_wgrad_cfg<128, 128, 2, 2, true, PRE>(a, splits, st);
+    default: return launch_wgrad_cfg<128, 128, 2, 2, false, PRE>(a, splits, st);
+  }
+}
+
 int launch_wgrad_fast(FastWgradArgs a, int splits, hipStream_t st) {
   const long nkt = (a.Kpix + kWgBK - 1) / kWgBK;
   a.kt_per_split = (int)((nkt + splits - 1) / splits);
-  if (wgrad_ring_ok(a)) return launch_wgrad_ring(a, splits, st);
-  static const bool no_row = getenv("UNETSEG_WG_NO_ROW32") != nullptr;
-  // ROW32: every K step is one 32-pixel run of an output row, and the per-lane pixel deltas and
-  // scalar bases fit 32-bit offsets (the caller bounds both tensors below 2^31 bytes)
-  const bool row32 = !no_row && a.Q % kWgBK == 0;
-  if (a.in_sc) {
-    if (a.Cout <= 64) {
-      if (row32) launch_wgrad_cfg<64, 256, 1, 4, true, true>(a, splits, st);
-      else launch_wgrad_cfg<64, 256, 1, 4, false, true>(a, splits, st);
-    } else {
-      if (row32) launch_wgrad_cfg<128, 128, 2, 2, true, true>(a, splits, st);
-      else launch_wgrad_cfg<128, 128, 2, 2, false, true>(a, splits, st);
-    }
-    return 0;
-  }
-  if (a.Cout <= 64) {
-    if (row32) launch_wgrad_cfg<64, 256, 1, 4, true>(a, splits, st);
-    else launch_wgrad_cfg<64, 256, 1, 4, false>(a, splits, st);
-  } else {
-    if (row32) launch_wgrad_cfg<128, 128, 2, 2, true>(a, splits, st);
-    else launch_wgrad_cfg<128, 128, 2, 2, false>(a, splits, st);
-  }
+  const int kind = wgrad_fast_kind(a);
+  if (kind == kWgRing64x256 || kind == kWgRing128) return launch_wgrad_ring(a, splits, st);
+  if (a.in_sc) launch_wgrad_kind<true>(kind, a, splits, st);
+  else launch_wgrad_kind<false>(kind, a, splits, st);
   return 0;
 }
