@@ -139,6 +139,7 @@ class Recorder:
             with torch.cuda.stream(main):
                 for i, node in cell.get("nodes", ()):
                     g = node.grad
+                    # node.fused (an ops.Partials): a consumer's backward already masked this gradient
                     cap[i] = (g.detach().clone() if g is not None else None, node.fused is not None)
                 for i, holder in cell.get("holders", ()):
                     g = holder.get("grad")

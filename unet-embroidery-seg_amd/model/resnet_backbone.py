@@ -51,7 +51,8 @@ class Bottleneck(nn.Module):
 def run_bottleneck(ctx, b, x):
     # conv1 is recorded before the downsample conv: in the reversed tape it delivers the last
     # contribution to x.grad (after the decoder's skip concat and the downsample branch), so it can
-    # run the previous block's residual BN backward pass 1 in its epilogue (ops._dgrad_fused_res).
+    # run the previous block's residual BN backward pass 1 in its epilogue (ops._dgrad_fused_res, from
+    # the POST_RES_BN_RELU Producer record that block's bn3 left on x).
     # A stride-2 downsample data gradient that initialises x.grad writes zeros on the parity
     # classes it does not reach.
     a1 = ops.conv_bn(ctx, x, b.conv1._pc, b.bn1)

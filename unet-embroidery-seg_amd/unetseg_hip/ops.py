@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from .lib import DT_BF16, DT_F32, lib
+from .lib import DT_BF16, DT_F32, last_error, lib
 from .lib import dgrad_config as _dgrad_config
 
 BN_TILE = 128  # == unetseg_conv_tile_m(): M tile of the conv kernel, hence of its BN partials
@@ -28,6 +28,11 @@ def P(t):
 def ldp(t):
     """pixel stride (elements) of an NHWC view"""
     return 0 if t is None else t.stride(-2)
+
+
+def PA(o, name):
+    """P(o.<name>); 0 when o is None (the BN state of an absent second branch)"""
+    return 0 if o is None else P(getattr(o, name))
 
 
 _QMEMO = {}
@@ -49,16 +54,46 @@ def _q(name, *args):
     return v
 
 
+#: Producer.kind.  The values are the C ABI's post codes (unetseg_conv2d_dgrad_post takes the kind
+#: verbatim); POST_RELU_BITS is never stored: the consumer picks it over POST_RELU when the record
+#: carries the packed mask and the shape has the kernel (_dgrad_fused)
+POST_RELU, POST_BN_RELU, POST_RES_BN_RELU, POST_RELU_BITS = 1, 2, 3, 4
+
+
+class Producer:
+    """The ReLU that produced a node, as the consumer's backward needs it to apply that ReLU's mask:
+    POST_RELU (conv + ReLU): ``act`` is the output itself, ``mbits`` its packed mask when the conv stored
+    one (unetseg_conv2d_fwd_mask); POST_BN_RELU: ``act`` is the BN input, ``st`` its BNState;
+    POST_RES_BN_RELU (residual BN-add-ReLU): also ``mbits`` and, with a BN on the shortcut, ``act2`` / ``st2``."""
+
+    __slots__ = ("kind", "act", "st", "mbits", "act2", "st2")
+
+    def __init__(self, kind, act, st=None, mbits=None, act2=None, st2=None):
+        self.kind, self.act, self.st, self.mbits, self.act2, self.st2 = kind, act, st, mbits, act2, st2
+
+
+class Partials:
+    """What a consumer's backward left for the producer's: ``part`` [rows][nq][C] row partials of the
+    masked gradient it stored in the node's gradient buffer (nq 2: sum dz and sum dz*xhat, or the bias
+    partials of a plain ReLU; 3: also sum dz*xhat2 of a shortcut BN)"""
+
+    __slots__ = ("part", "rows", "nq")
+
+    def __init__(self, part, rows, nq=2):
+        self.part, self.rows, self.nq = part, rows, nq
+
+
 class Node:
-    """An activation.  ``uses`` counts the ops that consumed it; ``fuse`` describes the ReLU that
-    produced it, so that a sole consumer conv can apply that op's backward mask and first reduction
-    in its data-gradient epilogue (``fused`` then holds the partials for the producer's backward).
+    """An activation.  ``uses`` counts the ops that consumed it; ``fuse`` (a Producer) describes the
+    ReLU that produced it, so that a consumer whose backward delivers the node's whole gradient can apply
+    that op's backward mask and first reduction (a conv in its data-gradient epilogue, the upsample and
+    head backwards); ``fused`` (a Partials) then holds what it wrote, for the producer's backward.
     ``lazy`` (a BNState): the node stands for relu(BN(data)) that was never stored -- ``data`` is the
     BN input and the consuming conv applies BN-ReLU on load (``bn(..., lazy=True)``).  ``kpad`` (Kp > K):
     the gradient buffer is allocated as the first K channels of a zeroed Kp-channel tensor (``gpad``),
     which the producing conv's padded-K backward reads as it is (see conv)."""
 
-    __slots__ = ("data", "grad", "need_grad", "uses", "fuse", "fused", "lazy", "head", "mbits", "kpad", "gpad")
+    __slots__ = ("data", "grad", "need_grad", "uses", "fuse", "fused", "lazy", "head", "kpad", "gpad")
 
     def __init__(self, data, need_grad=True):
         self.data = data
@@ -69,7 +104,6 @@ class Node:
         self.fused = None
         self.lazy = None
         self.head = None  # (head Conv2d, fp32 logits) computed by the producing conv's epilogue
-        self.mbits = None  # packed ReLU mask of data (unetseg_conv2d_fwd_mask), read by post 4
         self.kpad = 0
         self.gpad = None
 
@@ -450,6 +484,37 @@ def _dgrad_launches(ctx, ldy, N, Pq, Qq, K, C, R, S, stride, pad, H, W):
     return len(cfgs) - merged + (1 if merged else 0)
 
 
+def _conv_geom(pc, X1, X2):
+    """(N, H, W, C1, C2, Pq, Qq, M, desc, flops) of pc applied to cat[X1, X2].  desc is the probe
+    descriptor (N, H, W, C1, C2, K, R, S, stride, pad, ld1, ld2): bench/tools map it to the kernel
+    configuration through the unetseg_conv2d_*_config queries; flops is algorithmic (unpadded Cin)"""
+    stride, pad = pc.conv.stride, pc.conv.padding
+    N, H, W, C1 = X1.shape
+    C2 = X2.shape[-1] if X2 is not None else 0
+    Pq = (H + 2 * pad - pc.R) // stride + 1
+    Qq = (W + 2 * pad - pc.S) // stride + 1
+    M = N * Pq * Qq
+    desc = (N, H, W, C1, C2, pc.K, pc.R, pc.S, stride, pad, ldp(X1), ldp(X2))
+    return N, H, W, C1, C2, Pq, Qq, M, desc, 2.0 * M * pc.K * pc.C * pc.R * pc.S
+
+
+def _wgrad_stream(ctx, ws_bytes, reads, serial=False):
+    """where a weight gradient runs: the side stream when the backward overlaps (the launch needs only
+    dY and the layer's inputs, and nothing in the data-gradient chain reads its output), the compute
+    stream otherwise or when serial.  reads: the tensors the launch reads.  Returns (side stream or
+    None, workspace, stream handle)"""
+    side = None if serial else ctx.side
+    if side is None:
+        return None, workspace(ws_bytes, ctx.device), ctx.stream
+    lib.stream_wait(side.cuda_stream, ctx.stream)
+    # the tensors may be freed (compute-stream order) before the launch has run on the side stream,
+    # which lags the compute stream
+    for t in reads:
+        if t is not None:
+            t.record_stream(side)
+    return side, workspace(ws_bytes, ctx.device, 1), side.cuda_stream
+
+
 def conv(ctx, x1, pc, x2=None, relu=False, stats=False, out=None, head=None):
     """y = conv(cat[x1, x2]) (+bias if the conv has one, ReLU).  Stride/padding come from the
     Conv2d container.  out: an NHWC view (pixel stride >= K) to write y into, e.g. a channel slice
@@ -468,13 +533,9 @@ def conv(ctx, x1, pc, x2=None, relu=False, stats=False, out=None, head=None):
     last_grad = x1.uses == 1
     layer = ctx.layer
     X1 = x1.data
-    N, H, W, C1 = X1.shape
     X2 = x2.data if x2 is not None else None
-    C2 = X2.shape[-1] if X2 is not None else 0
     K, R, S = pc.K, pc.R, pc.S
-    Pq = (H + 2 * pad - R) // stride + 1
-    Qq = (W + 2 * pad - S) // stride + 1
-    M = N * Pq * Qq
+    N, H, W, C1, C2, Pq, Qq, M, desc, flops = _conv_geom(pc, X1, X2)
     y = ctx.empty(N, Pq, Qq, K) if out is None else out
     st = None
     stats = stats and ctx.training  # eval-mode BN normalises with the running statistics
@@ -482,10 +543,6 @@ def conv(ctx, x1, pc, x2=None, relu=False, stats=False, out=None, head=None):
         tile = _q("conv2d_fwd_tile_m", ctx.dt, C1, ldp(X1), C2, ldp(X2), N, H, W, K, R, S, stride, pad)
         st = (ctx.f32(math.ceil(M / tile), 2, K), tile)  # [row tiles][sum, M2][K]
     b = pc.conv.bias
-    flops = 2.0 * M * K * pc.C * R * S  # algorithmic (unpadded Cin)
-    # probe descriptor: (N, H, W, C1, C2, K, R, S, stride, pad, ld1, ld2); bench/tools map it to the
-    # kernel configuration through the unetseg_conv2d_*_config queries
-    desc = (N, H, W, C1, C2, K, R, S, stride, pad, ldp(X1), ldp(X2))
     mbits = None
     if lazy is not None:
         with _probe("igemm_tn", flops, 1, ("fwd_bnrelu_in",) + desc):
@@ -511,7 +568,7 @@ def conv(ctx, x1, pc, x2=None, relu=False, stats=False, out=None, head=None):
                 rc = lib.conv2d_fwd_mask(ctx.dt, P(X1), ldp(X1), N, H, W, P(pc.wk), P(b), P(y), ldp(y), P(mbits),
                                          ctx.stream)
             if rc != 0:
-                raise RuntimeError(f"unetseg_conv2d_fwd_mask failed ({rc}): {lib_last_error()}")
+                raise RuntimeError(f"unetseg_conv2d_fwd_mask failed ({rc}): {last_error()}")
         else:
             with _probe("igemm_tn", flops, 1, ("fwd",) + desc):
                 lib.conv2d_fwd(ctx.dt, P(X1), C1, ldp(X1), P(X2), C2, ldp(X2), N, H, W, P(pc.wk), K, R, S, stride,
@@ -520,23 +577,19 @@ def conv(ctx, x1, pc, x2=None, relu=False, stats=False, out=None, head=None):
     out.head = head
     if x2 is None and pc.padk(ctx.dt):
         out.kpad = -(-K // 64) * 64
-    if mbits is not None:
-        out.mbits = mbits
     if relu:
-        out.fuse = (1, y, None)
+        out.fuse = Producer(POST_RELU, y, mbits=mbits)
     _tap(ctx, "conv", out, [x1, x2], conv=pc.conv, relu=relu)
 
     def bwd():
         dA = out.grad
         if dA is None:
             return
-        dev = ctx.device
         if relu and out.fused is not None:
             # the consumer's dgrad stored the masked gradient and the bias partials
-            part, rows = out.fused
             dY = dA
             if b is not None:
-                part, rows, _ = _merge_rows(ctx, part, K, rows, 2)
+                part, rows, _ = _merge_rows(ctx, out.fused.part, K, out.fused.rows, 2)
                 lib.colsum_rows(P(part), K, rows, 0, P(b.grad), 1, ctx.stream)
         elif relu:
             Gr = _q("reduce_tiles", ctx.dt, M, K, None, None)
@@ -559,28 +612,17 @@ def conv(ctx, x1, pc, x2=None, relu=False, stats=False, out=None, head=None):
             if out.gpad is not None and dY is out.grad:
                 dY = out.gpad
             else:
-                dYp = torch.zeros(N, Pq, Qq, Kp, dtype=ctx.tdtype, device=dev)
+                dYp = torch.zeros(N, Pq, Qq, Kp, dtype=ctx.tdtype, device=ctx.device)
                 lib.add(ctx.dt, P(dY), ldp(dY), P(dYp), Kp, M, K, ctx.stream)
                 dY = dYp
         cin = C1 + C2
 
         def launch_wgrad(serial=False):
-            """weight gradient: on the side stream when overlapping (it only needs dY and the inputs,
-            and nothing in the data-gradient chain reads its output); returns that stream or None"""
+            """weight gradient (_wgrad_stream: it reads dY, the inputs and the input prologue's BN
+            coefficients); returns the side stream it ran on or None"""
             ws_bytes = _q("conv2d_wgrad_workspace", ctx.dt, N, Pq, Qq, Kp, cin, R, S)
-            side = None if serial else ctx.side
-            if side is not None:
-                lib.stream_wait(side.cuda_stream, ctx.stream)
-                # dY, the inputs and the input prologue's BN coefficients may be freed (compute-stream
-                # order) before the wgrad has run on the side stream, which lags the compute stream
-                for t in (dY, X1, X2) + ((lazy.sc, lazy.sh) if lazy is not None else ()):
-                    if t is not None:
-                        t.record_stream(side)
-                ws = workspace(ws_bytes, dev, 1)
-                wst = side.cuda_stream
-            else:
-                ws = workspace(ws_bytes, dev)
-                wst = ctx.stream
+            reads = (dY, X1, X2) + ((lazy.sc, lazy.sh) if lazy is not None else ())
+            side, ws, wst = _wgrad_stream(ctx, ws_bytes, reads, serial)
             if Kp != K:
                 # the Kp-row GEMM (dY's padded columns are zero) reduced straight into the K-row gradient
                 with _probe("wgrad", flops, 1, ("wgrad_padk",) + desc, stream=side):
@@ -664,21 +706,17 @@ def conv_bn(ctx, x, pc, bnm, x2=None, lazy=False):
     if ctx.training or ctx.tape is not None or not BN_FOLD or ctx.dt != DT_F32:
         y, st = conv(ctx, x, pc, x2=x2, stats=True)
         return bn(ctx, y, st, bnm, relu=True, lazy=lazy)
-    K, C, R, S = pc.K, pc.C, pc.R, pc.S
+    K, R, S = pc.K, pc.R, pc.S
     kscale, bias = ctx.f32(K), ctx.f32(K)
     lib.bn_fold(K, P(bnm.weight), P(bnm.bias), P(bnm.running_mean), P(bnm.running_var), bnm.eps, P(pc.conv.bias),
                 P(kscale), P(bias), ctx.stream)
     use(x, x2)
     X1, X2 = x.data, (x2.data if x2 is not None else None)
-    N, H, W, C1 = X1.shape
-    C2 = X2.shape[-1] if X2 is not None else 0
-    stride, pad = pc.conv.stride, pc.conv.padding
-    Pq, Qq = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
+    N, H, W, C1, C2, Pq, Qq, _, desc, flops = _conv_geom(pc, X1, X2)
     y = ctx.empty(N, Pq, Qq, K)
-    desc = (N, H, W, C1, C2, K, R, S, stride, pad, ldp(X1), ldp(X2))
-    with _probe("igemm_tn", 2.0 * N * Pq * Qq * K * C * R * S, 1, ("fwd_affine",) + desc):
-        lib.conv2d_fwd_affine(ctx.dt, P(X1), C1, ldp(X1), P(X2), C2, ldp(X2), N, H, W, P(pc.wk), K, R, S, stride, pad,
-                              P(kscale), P(bias), 1, P(y), K, ctx.stream)
+    with _probe("igemm_tn", flops, 1, ("fwd_affine",) + desc):
+        lib.conv2d_fwd_affine(ctx.dt, P(X1), C1, ldp(X1), P(X2), C2, ldp(X2), N, H, W, P(pc.wk), K, R, S,
+                              pc.conv.stride, pc.conv.padding, P(kscale), P(bias), 1, P(y), K, ctx.stream)
     return Node(y)
 
 
@@ -697,11 +735,13 @@ def _dgrad_fused_res(ctx, x1, dY, pc, N, H, W, C1, Pq, Qq, flops, desc, last_gra
     decoder's skip concat): when this conv delivers the last contribution, accumulate the dgrad onto
     x1.grad, mask with the stored ReLU bits and write BN3's backward partials in the epilogue (and the
     downsample BN's, block 0) -- the producer's bn_bwd_reduce pass over the gradient is not run."""
-    if not (FUSE_RES and x1.fuse is not None and x1.fuse[0] == 3 and x1.grad is not None and last_grad and
-            (x1.uses == 2 or (FUSE_RES_MULTI and x1.uses > 2)) and ctx.dt == DT_BF16 and (pc.R, pc.S) == (1, 1) and pc.conv.stride in (1, (1, 1)) and
+    p = x1.fuse
+    if not (FUSE_RES and p is not None and p.kind == POST_RES_BN_RELU and x1.grad is not None and last_grad and
+            (x1.uses == 2 or (FUSE_RES_MULTI and x1.uses > 2)) and ctx.dt == DT_BF16 and
+            (pc.R, pc.S) == (1, 1) and pc.conv.stride in (1, (1, 1)) and
             x1.grad.stride(-1) == 1 and ldp(x1.grad) % 8 == 0 and H == Pq and W == Qq):
         return False
-    _, y3, s1, mbits, y2, s2 = x1.fuse
+    y3, s1, y2, s2 = p.act, p.st, p.act2, p.st2
     K = pc.K
     g = x1.grad
     rows = _q("conv2d_dgrad_post_res", ctx.dt, 0, ldp(dY), N, Pq, Qq, 0, K, C1, 0, ldp(g), 0, ldp(y3),
@@ -712,10 +752,19 @@ def _dgrad_fused_res(ctx, x1, dY, pc, N, H, W, C1, Pq, Qq, flops, desc, last_gra
     part = ctx.f32(rows, nq, C1)
     with _probe("igemm_tn", flops, 1, ("dgrad_post3",) + desc):
         lib.conv2d_dgrad_post_res(ctx.dt, P(dY), ldp(dY), N, Pq, Qq, P(pc.wt), K, C1, P(g), ldp(g), P(y3), ldp(y3),
-                                  P(s1.mean), P(s1.inv), P(mbits), P(y2), ldp(y2), P(s2.mean if s2 else None),
-                                  P(s2.inv if s2 else None), P(part), rows, ctx.stream)
-    x1.fused = (part, rows, nq)
+                                  P(s1.mean), P(s1.inv), P(p.mbits), P(y2), ldp(y2), PA(s2, "mean"), PA(s2, "inv"),
+                                  P(part), rows, ctx.stream)
+    x1.fused = Partials(part, rows, nq)
     return True
+
+
+def _sole_relu_consumer(ctx, x):
+    """x is a ReLU or plain BN-ReLU output (x.fuse) and the calling op its only consumer: that op's
+    backward yields x's whole gradient, so it may apply the ReLU's mask and write x.fused.  What the three
+    fused backwards share; each adds its own conditions (a residual output: _dgrad_fused_res)"""
+    p = x.fuse
+    return (FUSE and p is not None and p.kind != POST_RES_BN_RELU and x.grad is None and x.uses == 1 and
+            ctx.dt == DT_BF16)
 
 
 def _dgrad_fused(ctx, x1, dY, pc, N, H, W, C1, Pq, Qq, flops, desc, last_grad=False):
@@ -724,21 +773,23 @@ def _dgrad_fused(ctx, x1, dY, pc, N, H, W, C1, Pq, Qq, flops, desc, last_grad=Fa
     is x1's whole gradient) and the shape has a fused kernel; returns False otherwise."""
     if _dgrad_fused_res(ctx, x1, dY, pc, N, H, W, C1, Pq, Qq, flops, desc, last_grad):
         return True
-    if not (FUSE and x1.fuse is not None and x1.fuse[0] != 3 and x1.grad is None and x1.uses == 1 and
-            ctx.dt == DT_BF16):
+    # nothing beyond the shared test: the kernel has post 1 / 4 and post 2, and its mask comes from the
+    # record's own tensors (act, st, mbits), never from x1.data, so the two need not still agree
+    if not _sole_relu_consumer(ctx, x1):
         return False
-    kind, aux, st = x1.fuse
+    p = x1.fuse
+    kind, aux, st = p.kind, p.act, p.st
     K, R, S = pc.K, pc.R, pc.S
     stride, pad = pc.conv.stride, pc.conv.padding
     args = [ctx.dt, P(dY), ldp(dY), N, Pq, Qq, P(pc.wt), K, C1, R, S, stride, pad]
-    coeffs = [P(st.sc), P(st.sh), P(st.mean), P(st.inv)] if kind == 2 else [0, 0, 0, 0]
+    coeffs = [P(st.sc), P(st.sh), P(st.mean), P(st.inv)] if kind == POST_BN_RELU else [0, 0, 0, 0]
     qargs = (ctx.dt, 0, ldp(dY), N, Pq, Qq, 0, K, C1, R, S, stride, pad, 0, C1, H, W)
     rows = -1
-    if kind == 1 and x1.mbits is not None:
+    if kind == POST_RELU and p.mbits is not None:
         # the producer stored its ReLU mask as bits: post 4 reads them instead of the activation
-        rows = _q("conv2d_dgrad_post", *qargs, 4, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+        rows = _q("conv2d_dgrad_post", *qargs, POST_RELU_BITS, 0, 0, 0, 0, 0, 0, 0, 0, 0)
         if rows > 0:
-            kind, aux = 4, x1.mbits
+            kind, aux = POST_RELU_BITS, p.mbits
     if rows <= 0:
         rows = _q("conv2d_dgrad_post", *qargs, kind, 0, ldp(aux), 0, 0, 0, 0, 0, 0, 0)
     if rows <= 0:
@@ -747,18 +798,13 @@ def _dgrad_fused(ctx, x1, dY, pc, N, H, W, C1, Pq, Qq, flops, desc, last_grad=Fa
     part = ctx.f32(rows, 2, C1)
     with _probe("igemm_tn", flops, _dgrad_launches(ctx, ldp(dY), N, Pq, Qq, K, C1, R, S, stride, pad, H, W),
                 (f"dgrad_post{kind}",) + desc):
-        rc = lib.conv2d_dgrad_post(*args, P(g), C1, H, W, kind, P(aux), 0 if kind == 4 else ldp(aux), *coeffs,
-                                   P(part), rows, ctx.stream)
+        rc = lib.conv2d_dgrad_post(*args, P(g), C1, H, W, kind, P(aux), 0 if kind == POST_RELU_BITS else ldp(aux),
+                                   *coeffs, P(part), rows, ctx.stream)
     if rc != 0:
-        raise RuntimeError(f"unetseg_conv2d_dgrad_post failed ({rc}): {lib_last_error()}")
+        raise RuntimeError(f"unetseg_conv2d_dgrad_post failed ({rc}): {last_error()}")
     x1.grad = g
-    x1.fused = (part, rows)
+    x1.fused = Partials(part, rows)
     return True
-
-
-def lib_last_error():
-    from .lib import last_error
-    return last_error()
 
 
 #: the 7x7/s2 ResNet stem on the fast kernels in bf16 (UNETSEG_NO_FAST_STEM=1: generic conv path)
@@ -796,16 +842,7 @@ def stem_conv(ctx, x, conv_mod):
         if dY is None:
             return
         ws_bytes = lib.stem_wgrad_workspace(N, H, W, K)
-        side = None if "stem" in WG_SERIAL_LAYERS else ctx.side
-        if side is not None:
-            lib.stream_wait(side.cuda_stream, ctx.stream)
-            for t in (dY, xp):
-                t.record_stream(side)
-            ws = workspace(ws_bytes, ctx.device, 1)
-            wst = side.cuda_stream
-        else:
-            ws = workspace(ws_bytes, ctx.device)
-            wst = ctx.stream
+        side, ws, wst = _wgrad_stream(ctx, ws_bytes, (dY, xp), serial="stem" in WG_SERIAL_LAYERS)
         with _probe("wgrad", flops, 1, ("stem_wgrad",) + desc, stream=side):
             lib.stem_wgrad(P(xp), N, H, W, P(dY), ldp(dY), K, P(ws), ws.numel(), P(conv_mod.weight.grad), C, 1, wst)
         ctx.param_done(conv_mod.weight, stream=side)
@@ -876,6 +913,28 @@ def _materialize(ctx, node):
     node.lazy = None
 
 
+def _bn_bwd_reduce(ctx, dA, Y, s1, M, C, part, Gr, Y2=None, s2=None, mask=None, remask=False):
+    """unetseg_bn_bwd_reduce: part [3][C][Gr] = column partials of (dz, dz*xhat1, dz*xhat2), dz = mask * dA.
+    mask: (pointer, pixel stride) of what the ReLU mask is read from -- the activation, or packed bits
+    with stride 0; None: nothing stored, and remask says whether the mask is recomputed from BN(Y) with
+    s1's coefficients (plain BN-ReLU) or dA is taken as it is (no ReLU, or dA already masked).  Y2 / s2:
+    the input and BNState of the second BN branch, or None"""
+    mA, lda = mask or (0, C)
+    lib.bn_bwd_reduce(ctx.dt, P(dA), ldp(dA), mA, lda, P(s1.sc) if remask else 0, P(s1.sh) if remask else 0, P(Y),
+                      ldp(Y), P(s1.mean), P(s1.inv), P(Y2), ldp(Y2), PA(s2, "mean"), PA(s2, "inv"), M, C, P(part), Gr,
+                      ctx.stream)
+
+
+def _bn_bwd_apply(ctx, dA, coef, Y, s1, dy1, M, C, Y2=None, s2=None, dy2=None, mask=None, remask=False, dz=None,
+                  dzacc=0):
+    """unetseg_bn_bwd_apply: dy1 (and dy2) from dA and the finalized coef; mask / remask / Y2 / s2 as in
+    _bn_bwd_reduce.  dz: where the masked gradient itself is written (dzacc: added) for a raw residual"""
+    mA, lda = mask or (0, C)
+    lib.bn_bwd_apply(ctx.dt, P(dA), ldp(dA), mA, lda, P(s1.sc) if remask else 0, P(s1.sh) if remask else 0, P(Y),
+                     ldp(Y), P(s1.mean), P(s1.inv), P(dy1), ldp(dy1), P(Y2), ldp(Y2), PA(s2, "mean"), PA(s2, "inv"),
+                     P(dy2), ldp(dy2), P(coef), P(dz), ldp(dz), dzacc, M, C, ctx.stream)
+
+
 def bn(ctx, y, st, bnm, relu=True, res=None, res_bn=None, lazy=False):
     """a = act(BN(y) [+ res | + BN2(y2)]).  y: conv output Node with partial stats st.
     res: raw residual Node; res_bn: (Node y2, stats2, bn module 2).  lazy (plain BN-ReLU in bf16
@@ -901,22 +960,22 @@ def bn(ctx, y, st, bnm, relu=True, res=None, res_bn=None, lazy=False):
         # residual BN-add-ReLU: the backward reads the packed ReLU mask (1/16 of the activation)
         a = ctx.empty(N, H, W, C)
         mbits = torch.empty(M * (C // 8), dtype=torch.uint8, device=ctx.device)
-        lib.bn_apply_mask(ctx.dt, P(Y), ldp(Y), P(s1.sc), P(s1.sh), P(R), ldp(R), P(s2.sc if s2 else None),
-                          P(s2.sh if s2 else None), mode, P(a), C, M, C, P(mbits), ctx.stream)
+        lib.bn_apply_mask(ctx.dt, P(Y), ldp(Y), P(s1.sc), P(s1.sh), P(R), ldp(R), PA(s2, "sc"), PA(s2, "sh"), mode,
+                          P(a), C, M, C, P(mbits), ctx.stream)
         out = Node(a)
         # a consumer conv that delivers this output's gradient last may run BN3's backward pass 1
         # (and the downsample BN's) in its data-gradient epilogue (_dgrad_fused_res)
-        out.fuse = (3, Y, s1, mbits, res_bn[0].data if res_bn is not None else None, s2)
+        out.fuse = Producer(POST_RES_BN_RELU, Y, s1, mbits, res_bn[0].data if res_bn is not None else None, s2)
     else:
         a = ctx.empty(N, H, W, C)
-        lib.bn_apply(ctx.dt, P(Y), ldp(Y), P(s1.sc), P(s1.sh), P(R), ldp(R), P(s2.sc if s2 else None),
-                     P(s2.sh if s2 else None), mode, int(relu), P(a), C, M, C, ctx.stream)
+        lib.bn_apply(ctx.dt, P(Y), ldp(Y), P(s1.sc), P(s1.sh), P(R), ldp(R), PA(s2, "sc"), PA(s2, "sh"), mode,
+                     int(relu), P(a), C, M, C, ctx.stream)
         out = Node(a)
     _tap(ctx, "bn", out, [y, res, res_bn[0] if res_bn is not None else None], bn=bnm,
          bn2=res_bn[2] if res_bn is not None else None, relu=relu, lazy=out.lazy is not None)
-    plain_relu = relu and res is None and res_bn is None
-    if plain_relu and ctx.training:
-        out.fuse = (2, Y, s1)
+    plain = relu and res is None and res_bn is None
+    if plain and ctx.training:
+        out.fuse = Producer(POST_BN_RELU, Y, s1)
 
     def bwd():
         dA = out.grad
@@ -924,70 +983,40 @@ def bn(ctx, y, st, bnm, relu=True, res=None, res_bn=None, lazy=False):
             return
         if not ctx.training:
             raise NotImplementedError("backward through eval-mode BatchNorm is not on the hot path")
-        if out.fused is not None and len(out.fused) == 3:
-            # residual BN-add-ReLU: the next block's conv1 dgrad stored dz = mask * dA in dA's buffer and
-            # the (sum dz, sum dz*xhat1 [, sum dz*xhat2]) row partials (_dgrad_fused_res)
-            part, rows, nq = out.fused
-            part, rows, _ = _merge_rows(ctx, part, C, rows, nq)
-            coef = ctx.f32(6, C)
-            b2 = res_bn[2] if res_bn is not None else None
-            y2 = res_bn[0] if res_bn is not None else None
-            lib.bn_bwd_finalize_rows_res(P(part), C, rows, M, nq - 1, P(bnm.weight), P(s1.inv), P(bnm.weight.grad),
-                                         P(bnm.bias.grad), P(b2.weight if b2 else None), P(s2.inv if s2 else None),
-                                         P(b2.weight.grad if b2 else None), P(b2.bias.grad if b2 else None), P(coef),
-                                         ctx.stream)
-            ctx.param_done(bnm.weight, bnm.bias)
-            if b2 is not None:
-                ctx.param_done(b2.weight, b2.bias)
-            dy1, acc1 = gbuf(ctx, y)
-            assert acc1 == 0
-            dy2 = Y2 = None
-            if y2 is not None:
-                Y2 = y2.data
-                dy2, acc2 = gbuf(ctx, y2)
-                assert acc2 == 0
-            if res is not None and res.need_grad:
-                # the residual gradient IS dz: the block input's gradient starts as this buffer (the
-                # block's conv1 dgrad accumulates onto it later; nothing reads dz after this apply)
-                assert res.grad is None
-                res.grad = dA
-            lib.bn_bwd_apply(ctx.dt, P(dA), ldp(dA), 0, C, 0, 0, P(Y), ldp(Y), P(s1.mean), P(s1.inv), P(dy1), ldp(dy1),
-                             P(Y2), ldp(Y2), P(s2.mean if s2 else None), P(s2.inv if s2 else None), P(dy2), ldp(dy2),
-                             P(coef), 0, 0, 0, M, C, ctx.stream)
-            return
-        if out.fused is not None:
-            # the consumer's dgrad stored dz = dA * mask and the (sum dz, sum dz*xhat) row partials
-            part, rows = out.fused
-            part, rows, _ = _merge_rows(ctx, part, C, rows, 2)
-            coef = ctx.f32(6, C)
-            lib.bn_bwd_finalize_rows(P(part), C, rows, M, P(bnm.weight), P(s1.inv), P(bnm.weight.grad),
-                                     P(bnm.bias.grad), P(coef), ctx.stream)
-            ctx.param_done(bnm.weight, bnm.bias)
-            dy1, acc1 = gbuf(ctx, y)
-            assert acc1 == 0
-            lib.bn_bwd_apply(ctx.dt, P(dA), ldp(dA), 0, C, 0, 0, P(Y), ldp(Y), P(s1.mean), P(s1.inv),
-                             P(dy1), ldp(dy1), 0, 0, 0, 0, 0, 0, P(coef), 0, 0, 0, M, C, ctx.stream)
-            return
-        Gr = _q("reduce_tiles", ctx.dt, M, C, None, None)
-        part = ctx.f32(3, C, Gr)
-        y2 = res_bn[0] if res_bn is not None else None
+        y2, b2 = (res_bn[0], res_bn[2]) if res_bn is not None else (None, None)
         Y2 = y2.data if y2 is not None else None
-        # plain BN-ReLU: the mask is recomputed from y (no read of the activation)
-        plain = relu and res is None and res_bn is None
-        mA = 0 if (plain or not relu) else P(out.data)
-        lda = C
-        if mbits is not None:  # the packed mask written by the forward (lda 0 flags it)
-            mA, lda = P(mbits), 0
-        msc, msh = (P(s1.sc), P(s1.sh)) if plain else (0, 0)
-        lib.bn_bwd_reduce(ctx.dt, P(dA), ldp(dA), mA, lda, msc, msh, P(Y), ldp(Y), P(s1.mean), P(s1.inv),
-                          P(Y2), ldp(Y2), P(s2.mean if s2 else None), P(s2.inv if s2 else None), M, C, P(part), Gr,
-                          ctx.stream)
-        coef = ctx.f32(6, C)
-        nb = 2 if y2 is not None else 1
-        b2 = res_bn[2] if res_bn is not None else None
-        lib.bn_bwd_finalize(P(part), C, Gr, M, nb, P(bnm.weight), P(s1.inv), P(bnm.weight.grad), P(bnm.bias.grad),
-                            P(b2.weight if b2 else None), P(s2.inv if s2 else None),
-                            P(b2.weight.grad if b2 else None), P(b2.bias.grad if b2 else None), P(coef), ctx.stream)
+        # how coef is produced.  All three finalizes take the second branch's (weight, inv, dweight, dbias)
+        bn2 = (P(b2.weight), P(s2.inv), P(b2.weight.grad), P(b2.bias.grad)) if b2 is not None else (0, 0, 0, 0)
+        f = out.fused
+        fused_res = f is not None and out.fuse.kind == POST_RES_BN_RELU
+        mask, dz, dzacc = None, None, 0
+        if f is not None:
+            # a consumer's backward stored dz = mask * dA in dA's buffer and its row partials: (sum dz,
+            # sum dz*xhat) from a sole consumer (_sole_relu_consumer), (sum dz, sum dz*xhat1 [, sum dz*xhat2])
+            # for a residual BN-add-ReLU from the next block's conv1 dgrad (_dgrad_fused_res).  No mask is left
+            # to apply (mA = 0, lda = C, msc = msh = 0)
+            part, rows, _ = _merge_rows(ctx, f.part, C, f.rows, f.nq)
+            coef = ctx.f32(6, C)
+            if fused_res:
+                lib.bn_bwd_finalize_rows_res(P(part), C, rows, M, f.nq - 1, P(bnm.weight), P(s1.inv),
+                                             P(bnm.weight.grad), P(bnm.bias.grad), *bn2, P(coef), ctx.stream)
+            else:
+                lib.bn_bwd_finalize_rows(P(part), C, rows, M, P(bnm.weight), P(s1.inv), P(bnm.weight.grad),
+                                         P(bnm.bias.grad), P(coef), ctx.stream)
+        else:
+            Gr = _q("reduce_tiles", ctx.dt, M, C, None, None)
+            part = ctx.f32(3, C, Gr)
+            # plain BN-ReLU: the mask is recomputed from y (no read of the activation); otherwise the packed
+            # mask written by the forward (pixel stride 0 flags it) or the activation itself
+            if mbits is not None:
+                mask = (P(mbits), 0)
+            elif relu and not plain:
+                mask = (P(out.data), C)
+            _bn_bwd_reduce(ctx, dA, Y, s1, M, C, part, Gr, Y2=Y2, s2=s2, mask=mask, remask=plain)
+            coef = ctx.f32(6, C)
+            lib.bn_bwd_finalize(P(part), C, Gr, M, 2 if y2 is not None else 1, P(bnm.weight), P(s1.inv),
+                                P(bnm.weight.grad), P(bnm.bias.grad), *bn2, P(coef), ctx.stream)
+        # shared tail
         ctx.param_done(bnm.weight, bnm.bias)
         if b2 is not None:
             ctx.param_done(b2.weight, b2.bias)
@@ -997,12 +1026,16 @@ def bn(ctx, y, st, bnm, relu=True, res=None, res_bn=None, lazy=False):
         if y2 is not None:
             dy2, acc2 = gbuf(ctx, y2)
             assert acc2 == 0
-        dz, dzacc = None, 0
         if res is not None and res.need_grad:
-            dz, dzacc = gbuf(ctx, res)
-        lib.bn_bwd_apply(ctx.dt, P(dA), ldp(dA), mA, lda, msc, msh, P(Y), ldp(Y), P(s1.mean), P(s1.inv),
-                         P(dy1), ldp(dy1), P(Y2), ldp(Y2), P(s2.mean if s2 else None), P(s2.inv if s2 else None),
-                         P(dy2), ldp(dy2), P(coef), P(dz), ldp(dz), dzacc, M, C, ctx.stream)
+            if fused_res:
+                # the residual gradient IS dz: the block input's gradient starts as this buffer (the
+                # block's conv1 dgrad accumulates onto it later; nothing reads dz after this apply)
+                assert res.grad is None
+                res.grad = dA
+            elif f is None:
+                dz, dzacc = gbuf(ctx, res)
+        _bn_bwd_apply(ctx, dA, coef, Y, s1, dy1, M, C, Y2=Y2, s2=s2, dy2=dy2, mask=mask, remask=plain and f is None,
+                      dz=dz, dzacc=dzacc)
 
     ctx.push(bwd)
     return out
@@ -1056,12 +1089,29 @@ def upsample2x(ctx, x, align_corners):
     return out
 
 
+def _is_relu_of(x, X):
+    # x's record is a plain conv + ReLU and still describes X: a kernel that reads the mask from X itself
+    # (not from the record's tensors) may stand in for that ReLU's backward
+    return x.fuse.kind == POST_RELU and x.fuse.act is X
+
+
+def _upsample_may_fuse(ctx, x, X):
+    # beyond the shared test: upsample2x_bwd_relu has the plain ReLU only and masks with X (_is_relu_of);
+    # FUSE_UP is this fusion's own switch
+    return FUSE_UP and _sole_relu_consumer(ctx, x) and _is_relu_of(x, X)
+
+
+def _head_may_fuse(ctx, x, X):
+    # beyond the shared test: pw_small_bwd_relu has the plain ReLU only and masks with X (_is_relu_of); it
+    # writes x's gradient unconditionally, so x must want one
+    return x.need_grad and _sole_relu_consumer(ctx, x) and _is_relu_of(x, X)
+
+
 def _upsample_bwd(ctx, x, gout, align_corners):
     """x.grad (+)= the backward of y = upsample2x(x) for the gradient gout of y"""
     X = x.data
     N, H, W, C = X.shape
-    if (FUSE and FUSE_UP and ctx.dt == DT_BF16 and x.fuse is not None and x.fuse[0] == 1 and x.fuse[1] is X
-            and x.grad is None and x.uses == 1):
+    if _upsample_may_fuse(ctx, x, X):
         # x is a ReLU output consumed only here (unetUp conv2 -> next block's upsample): its
         # backward mask and the producer conv's bias-gradient partials ride along
         rows = _q("upsample2x_bwd_tiles", ctx.dt, N, H, W, C)
@@ -1070,7 +1120,7 @@ def _upsample_bwd(ctx, x, gout, align_corners):
         lib.upsample2x_bwd_relu(ctx.dt, P(gout), ldp(gout), N, H, W, C, int(align_corners), P(X), ldp(X), P(g),
                                 ldp(g), P(part), rows, ctx.stream)
         x.grad = g
-        x.fused = (part, rows)
+        x.fused = Partials(part, rows)
         return
     g, acc = gbuf(ctx, x)
     lib.upsample2x_bwd(ctx.dt, P(gout), ldp(gout), N, H, W, C, int(align_corners), P(g), ldp(g), acc, ctx.stream)
@@ -1160,20 +1210,9 @@ def pw_head(ctx, x, conv_mod):
         if dy is None:
             return
         dy = dy.contiguous().float()
-        if K > 2:
-            G = lib.pw_head_tiles(M)
-            pw, pb = ctx.f32(K, C, G), ctx.f32(K, G)
-            dx, acc = (gbuf(ctx, x) if x.need_grad else (None, 0))
-            lib.pw_head_bwd(ctx.dt, P(dy), P(X), ldp(X), M, H * W, C, K, P(conv_mod.weight), P(dx), ldp(dx), acc,
-                            P(pw), P(pb), ctx.stream)
-            lib.colsum_finalize(P(pw), K * C, G, P(conv_mod.weight.grad), 1, ctx.stream)
-            lib.colsum_finalize(P(pb), K, G, P(conv_mod.bias.grad), 1, ctx.stream)
-            ctx.param_done(conv_mod.weight, conv_mod.bias)
-            return
-        G = _q("pw_small_tiles", M)
+        G = lib.pw_head_tiles(M) if K > 2 else _q("pw_small_tiles", M)
         pw, pb = ctx.f32(K, C, G), ctx.f32(K, G)
-        if (FUSE and x.need_grad and x.fuse is not None and x.fuse[0] == 1 and x.fuse[1] is X
-                and x.grad is None and x.uses == 1 and ctx.dt == DT_BF16):
+        if K <= 2 and _head_may_fuse(ctx, x, X):
             # x is a ReLU output consumed only here: its backward mask and the producer conv's
             # bias-gradient partials ride along (conv() reads them back from x.fused)
             dx = ctx.empty(N, H, W, C)
@@ -1181,11 +1220,12 @@ def pw_head(ctx, x, conv_mod):
             lib.pw_small_bwd_relu(ctx.dt, P(dy), P(X), ldp(X), M, H * W, C, K, P(conv_mod.weight), P(dx), ldp(dx),
                                   P(pw), P(pb), P(part), ctx.stream)
             x.grad = dx
-            x.fused = (part, G)
+            x.fused = Partials(part, G)
         else:
             dx, acc = (gbuf(ctx, x) if x.need_grad else (None, 0))
-            lib.pw_small_bwd(ctx.dt, P(dy), P(X), ldp(X), M, H * W, C, K, P(conv_mod.weight), P(dx), ldp(dx), acc,
-                             P(pw), P(pb), ctx.stream)
+            head_bwd = lib.pw_head_bwd if K > 2 else lib.pw_small_bwd  # same arguments
+            head_bwd(ctx.dt, P(dy), P(X), ldp(X), M, H * W, C, K, P(conv_mod.weight), P(dx), ldp(dx), acc, P(pw),
+                     P(pb), ctx.stream)
         lib.colsum_finalize(P(pw), K * C, G, P(conv_mod.weight.grad), 1, ctx.stream)
         lib.colsum_finalize(P(pb), K, G, P(conv_mod.bias.grad), 1, ctx.stream)
         ctx.param_done(conv_mod.weight, conv_mod.bias)
@@ -1370,8 +1410,7 @@ def bn_relu_prefix(ctx, block, width, bnm, idx=None):
             raise NotImplementedError("backward through eval-mode BatchNorm is not on the hot path")
         Gr = lib.reduce_tiles(ctx.dt, M, C, None, None)
         part = ctx.f32(3, C, Gr)
-        lib.bn_bwd_reduce(ctx.dt, P(dA), ldp(dA), 0, C, P(s.sc), P(s.sh), P(Y), ldp(Y), P(s.mean), P(s.inv), 0, 0,
-                          0, 0, M, C, P(part), Gr, ctx.stream)
+        _bn_bwd_reduce(ctx, dA, Y, s, M, C, part, Gr, remask=True)
         coef = ctx.f32(6, C)
         dg, db = (bnm.weight.grad, bnm.bias.grad) if idx is None else (ctx.f32(C), ctx.f32(C))
         if idx is not None:
@@ -1384,8 +1423,7 @@ def bn_relu_prefix(ctx, block, width, bnm, idx=None):
                 bnm.bias.grad.add_(db.index_select(0, idx))
         ctx.param_done(bnm.weight, bnm.bias)
         dy = ctx.empty(N, H, W, C)
-        lib.bn_bwd_apply(ctx.dt, P(dA), ldp(dA), 0, C, P(s.sc), P(s.sh), P(Y), ldp(Y), P(s.mean), P(s.inv),
-                         P(dy), C, 0, 0, 0, 0, 0, 0, P(coef), 0, 0, 0, M, C, ctx.stream)
+        _bn_bwd_apply(ctx, dA, coef, Y, s, dy, M, C, remask=True)
         if block.grad is None:
             block.grad = torch.zeros_like(block.data)
         G_ = block.grad
