@@ -360,6 +360,18 @@ int unetseg_mc_loss_fwd(const float* out, const int64_t* tgt, int B, int C, long
 int unetseg_mc_loss_bwd(const float* out, const int64_t* tgt, int B, int C, long P, const float* cls_w,
                         long ignore_index, int focal, float alpha, float gamma, const float* dice_t, int ct,
                         float beta, float smooth, const void* ws, const float* gscale, float* dout, void* stream);
+/* Lovasz-softmax (Berman et al., CVPR 2018, Alg. 1, class-averaged softmax errors) of fp32 planar logits
+ * out [B][C][P], 2 <= C <= 32, against tgt int64 [B][P]; a label equal to ignore_index or outside [0, C) is
+ * invalid.  Per present class c: e = |[tgt == c] - softmax_c| over the valid pixels, sorted descending (ties:
+ * ascending pixel index), loss_c = sum_k e_(k) (J_k - J_{k-1}); a segment's loss is the mean over its present
+ * classes.  per_image != 0: one segment per image, loss = mean over the B images (an image without a valid
+ * pixel counts 0); per_image == 0: one segment of all B*P pixels.  dlogits (NULL: value only) fp32 [B][C][P] =
+ * d loss / d out for a unit upstream gradient, exactly 0 at invalid pixels.  B*P < 2^31.
+ * Workspace, with S segments of L keys and T = ceil(L / 4096) (per image S = B*C, L = P; else S = C, L = B*P):
+ * 16 B C P + 4 S T (256 + 2) + 8 S + 256 bytes. */
+size_t unetseg_lovasz_softmax_workspace(int B, int C, long P, int per_image);
+int unetseg_lovasz_softmax_fwd(const float* out, const int64_t* tgt, int B, int C, long P, long ignore_index,
+                               int per_image, void* ws, size_t ws_bytes, float* dlogits, float* loss, void* stream);
 /* hist u64 [(C+1)][C] += (target row, argmax column); targets outside [0, C) count in row C */
 int unetseg_mc_confusion(const float* out, const int64_t* tgt, int B, int C, long P, unsigned long long* hist,
                          void* stream);

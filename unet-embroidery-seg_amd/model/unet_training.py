@@ -107,6 +107,12 @@ def Focal_Loss(inputs, target, cls_weights, num_classes=21, alpha=0.5, gamma=2):
     return losses.focal_loss(inputs, target, cls_weights, num_classes, alpha, gamma)
 
 
+def Lovasz_Softmax_Loss(inputs, target, num_classes=21, per_image=True):  # noqa: N802 - named like its neighbours
+    """Lovasz-softmax (Berman et al., CVPR 2018, Alg. 1), the multiclass form of lovasz_hinge_loss, with
+    CE_Loss's ignore_index = num_classes; per_image: mean of the per-image losses (fused HIP kernels)"""
+    return losses.lovasz_softmax_loss(inputs, target, num_classes, per_image)
+
+
 def Dice_loss(inputs, target, beta=1, smooth=1e-5):  # noqa: N802
     """unet_training.py:67-91: 1 - mean_c F-beta score of softmax vs the one-hot target (fused HIP kernel)"""
     return losses.dice_loss(inputs, target, beta, smooth)

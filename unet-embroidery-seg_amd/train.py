@@ -3,8 +3,8 @@
 Same command line, same `create_model` / `get_optimizer_and_lr` helpers and the same per-epoch
 flow: set the warm-cos LR, train (binary: utils.train_and_eval.train_one_epoch_binary; multitask:
 the fused seg+cls loop), validate, keep best/last `state_dict`s, write the metric history and a
-summary.  Tasks: binary, multiclass (CE / Focal (+ Dice), Mean-IoU model selection) and
-multitask.  Differences, all deliberate:
+summary.  Tasks: binary, multiclass (CE / Focal / Lovasz-softmax (+ Dice), Mean-IoU model selection)
+and multitask.  Differences, all deliberate:
   * the model, losses, metrics and Adam run on hand-written HIP kernels (no CPU fallback);
   * a real `--data-path` reads the HF parquet layout with utils/hf_dataloader.py: DataLoader
     workers decode and draw the augmentation, the pixel work runs on the GPU (DeviceLoader);
@@ -130,6 +130,9 @@ def _pos_weight_auto(train_ds, args, device):
 
 
 def train(args):
+    if args.loss == "lovasz_softmax" and args.task != "multiclass":
+        raise ValueError(f"--loss lovasz_softmax is the multiclass Lovasz loss; --task {args.task} takes "
+                         "lovasz_hinge (or bce)")
     rank, world, local = init_from_env("nccl")
     seed_everything(args.seed)
     num_classes = args.num_classes + 1 if args.task == "multiclass" else 2  # train.py:83-92
@@ -195,7 +198,8 @@ def train(args):
         else:  # train.py:285-294
             loss = train_one_epoch(model, optimizer, train_loader, device, args.use_dice, args.loss == "focal",
                                    torch.cuda.memory_allocated() / 2**20, num_classes,
-                                   scaler if args.amp else None, epoch, args.epochs)
+                                   scaler if args.amp else None, epoch, args.epochs,
+                                   lovasz_softmax=args.loss == "lovasz_softmax")
         train_losses.append(loss)
         if buckets is not None:
             buckets.sync_buffers()  # BN running statistics: rank 0's (DDP broadcast_buffers semantics)
@@ -210,7 +214,8 @@ def train(args):
                                       ignore_index=None, max_batches=mvb)
             score = float(metrics["IoU"])
         else:
-            metrics = evaluate(model, val_loader, device, args.use_dice, args.loss == "focal", num_classes)
+            metrics = evaluate(model, val_loader, device, args.use_dice, args.loss == "focal", num_classes,
+                               lovasz_softmax=args.loss == "lovasz_softmax")
             score = float(metrics["Mean IoU"])
         val_losses.append(metrics["Loss"])
         history.append(metrics)
@@ -279,7 +284,8 @@ def parse_args(argv=None):
     p.add_argument("--task", default="binary", choices=["binary", "multiclass", "multitask"])
     p.add_argument("--model", default="unet_resnet50", choices=sorted(SUPPORTED_MODELS.keys()))
     p.add_argument("--cls-loss-weight", default=1.0, type=float)
-    p.add_argument("--loss", default="lovasz_hinge", choices=["bce", "lovasz_hinge", "ce", "focal"])
+    p.add_argument("--loss", default="lovasz_hinge", choices=["bce", "lovasz_hinge", "ce", "focal", "lovasz_softmax"],
+                   help="lovasz_softmax: the multiclass task's IoU surrogate (--task multiclass only)")
     p.add_argument("--pos-weight", default="auto")
     p.add_argument("--pos-weight-samples", default=80, type=int)
     p.add_argument("--use-dice", action=argparse.BooleanOptionalAction, default=True)

@@ -110,6 +110,8 @@ SIGNATURES = {
     "unetseg_mc_loss_workspace": (SZ, [I, I, L]),
     "unetseg_mc_loss_fwd": (I, [P, P, I, I, L, P, L, I, F, F, P, I, F, F, P, SZ, P, P]),
     "unetseg_mc_loss_bwd": (I, [P, P, I, I, L, P, L, I, F, F, P, I, F, F, P, P, P, P]),
+    "unetseg_lovasz_softmax_workspace": (SZ, [I, I, L, I]),
+    "unetseg_lovasz_softmax_fwd": (I, [P, P, I, I, L, L, I, P, SZ, P, P, P]),
     "unetseg_mc_confusion": (I, [P, P, I, I, L, P, P]),
     "unetseg_softmax_resize_argmax": (I, [P, I, I, I, I, I, I, I, I, I, P, P]),
     "unetseg_resize_bilinear_fwd": (I, [I, P, I, I, I, I, I, I, I, I, P, I, P]),

@@ -5,6 +5,8 @@ logit difference (utils/train_and_eval.py:106-113) fused into the kernel:
   * "lovasz_hinge": per-image stable radix sort + Jaccard-gradient scan (model/unet_training.py:219-280)
   * "bce": BCE-with-logits mean, optional scalar pos_weight (model/unet_training.py:205-216)
 multitask_loss: seg BCE/Lovasz + w * CE over the cls head (model/unet_multitask.py:119-139).
+Multiclass task: ce_loss / focal_loss / dice_loss (one fused kernel pair) and lovasz_softmax_loss (the
+multiclass form of the Lovasz hinge, on the same segmented radix sort).
 """
 from __future__ import annotations
 
@@ -323,6 +325,52 @@ def dice_loss(inputs, target, beta=1, smooth=1e-5):
     """Dice_loss (model/unet_training.py:67-91) on a one-hot target [N,H,W,ct] (first C channels)"""
     inputs = _check_mc(inputs, target.shape[1:3])
     return _McLossFn.apply(inputs, None, None, MC_NONE, -1.0, 0.0, target, beta, smooth, -1)
+
+
+class _LovaszSoftmaxFn(torch.autograd.Function):
+    """unetseg_lovasz_softmax_fwd: softmax key generation, segmented radix sort per (image, class) or per
+    class, Jaccard-gradient scan and the softmax Jacobian, on fp32 planar logits [B][C][H][W].  The
+    forward leaves d loss / d logits for a unit upstream gradient; the backward scales it."""
+
+    @staticmethod
+    def forward(fctx, outputs, target, ignore_index, per_image):
+        if not outputs.is_cuda:
+            raise RuntimeError("HIP losses need device tensors")
+        out = outputs.detach().float().contiguous()
+        B, C = out.shape[0], out.shape[1]
+        Pn = out[0, 0].numel()
+        dev = out.device
+        tgt = target.detach().to(device=dev, dtype=torch.int64).contiguous()
+        if tgt.numel() != B * Pn:
+            raise ValueError(f"lovasz_softmax_loss: labels {tuple(target.shape)} do not match logits "
+                             f"{tuple(outputs.shape)}")
+        nb = lib.lovasz_softmax_workspace(B, C, Pn, int(bool(per_image)))
+        ws = workspace(nb, dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dl = torch.empty_like(out) if outputs.requires_grad else None
+        lib.lovasz_softmax_fwd(P(out), P(tgt), B, C, Pn, int(ignore_index), int(bool(per_image)), P(ws), ws.numel(),
+                               P(dl), P(loss), _stream(dev))
+        fctx.save_for_backward(dl)
+        fctx.meta = (outputs.shape, outputs.dtype)
+        return loss
+
+    @staticmethod
+    def backward(fctx, g):
+        (dl,) = fctx.saved_tensors
+        shape, dtype = fctx.meta
+        g = g.detach().float().reshape(1).contiguous()
+        dout = torch.empty(shape, dtype=torch.float32, device=dl.device)
+        lib.scale_grad(P(dl), dl.numel(), P(g), 1.0, 0, 0.0, P(dout), _stream(dl.device))
+        return dout.to(dtype), None, None, None
+
+
+def lovasz_softmax_loss(inputs, target, num_classes, per_image=True):
+    """Lovasz-softmax (Berman et al., CVPR 2018, Alg. 1; classes present in the segment, softmax errors):
+    the multiclass form of the Lovasz hinge.  Labels equal to num_classes (CE_Loss's ignore_index) or
+    outside the logits' classes are skipped.  per_image (default): the mean over the images of each
+    image's loss (an image without a valid pixel counts 0); else one loss over all pixels of the batch."""
+    inputs = _check_mc(inputs, target.shape[-2:])
+    return _LovaszSoftmaxFn.apply(inputs, target, num_classes, per_image)
 
 
 def mc_confusion(outputs, target, hist=None):

@@ -268,9 +268,11 @@ def frequency_weighted_iou(output, target, num_classes):
     return losses.mc_metrics_from_hist(_mc_hist(output, target))["Frequency Weighted IoU"]
 
 
-def _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss):
-    from model.unet_training import CE_Loss, Dice_loss, Focal_Loss
-    if focal_loss:
+def _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss, lovasz_softmax=False):
+    from model.unet_training import CE_Loss, Dice_loss, Focal_Loss, Lovasz_Softmax_Loss
+    if lovasz_softmax:
+        loss = Lovasz_Softmax_Loss(outputs, pngs, num_classes=num_classes)
+    elif focal_loss:
         loss = Focal_Loss(outputs, pngs, weights, num_classes=num_classes)
     else:
         loss = CE_Loss(outputs, pngs, weights, num_classes=num_classes)
@@ -280,8 +282,9 @@ def _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss)
 
 
 def train_one_epoch(model, optimizer, train_loader, device, dice_loss, focal_loss, gpu_used, num_classes, scaler,
-                    epoch, train_epoch):
-    """train_and_eval.py:308-409: CE or Focal (+ Dice) with unit class weights; returns the mean loss"""
+                    epoch, train_epoch, lovasz_softmax=False):
+    """train_and_eval.py:308-409: CE or Focal (+ Dice) with unit class weights; returns the mean loss.
+    lovasz_softmax: the per-image Lovasz-softmax is the main term instead of CE / Focal"""
     import numpy as np
     cls_weights = np.ones([num_classes], np.float32)
     epoch_loss = torch.zeros((), dtype=torch.float64, device=device)
@@ -294,13 +297,13 @@ def train_one_epoch(model, optimizer, train_loader, device, dice_loss, focal_los
         optimizer.zero_grad()
         if scaler is None:
             outputs = model_train(imgs)
-            loss = _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss)
+            loss = _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss, lovasz_softmax)
             loss.backward()
             optimizer.step()
         else:
             with autocast(device_type=device.type, enabled=True):
                 outputs = model_train(imgs)
-                loss = _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss)
+                loss = _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss, lovasz_softmax)
             scaler.scale(loss).backward()
             scaler.step(optimizer)
             scaler.update()
@@ -314,7 +317,7 @@ def train_one_epoch(model, optimizer, train_loader, device, dice_loss, focal_los
     return float(epoch_loss.item()) / max(n_batches, 1)
 
 
-def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes):
+def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lovasz_softmax=False):
     """train_and_eval.py:411-513: per-batch metrics averaged over batches, as the reference does"""
     import numpy as np
     weights = torch.tensor(np.ones([num_classes], np.float32)).to(device)
@@ -324,7 +327,8 @@ def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes):
         for batch in val_loader:
             imgs, pngs, labels = batch[0].to(device), batch[1].to(device), batch[2].to(device)
             outputs = model_eval(imgs)
-            loss_sum += _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss).double()
+            loss_sum += _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss,
+                                 lovasz_softmax).double()
             hists.append(losses.mc_confusion(outputs, pngs))
     n = max(len(val_loader), 1)
     keys = ("Pixel Accuracy", "Mean Accuracy", "Mean IoU", "Frequency Weighted IoU")

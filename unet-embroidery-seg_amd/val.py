@@ -61,7 +61,8 @@ def val(args):
         print(f"{m['Dice']:.4f}\t{m['IoU']:.4f}\t{m['Precision']:.4f}\t{m['Recall']:.4f}\t{m['Accuracy']:.4f}")
         return m
     if args.task == "multiclass":
-        m = evaluate(model, loader, device, dice_loss=True, focal_loss=False, num_classes=num_classes)
+        m = evaluate(model, loader, device, dice_loss=True, focal_loss=False, num_classes=num_classes,
+                     lovasz_softmax=args.loss == "lovasz_softmax")
         print(m)
         return m
 
@@ -103,7 +104,8 @@ def parse_args(argv=None):
     p.add_argument("--model", default="unet_resnet50", choices=sorted(SUPPORTED_MODELS.keys()))
     # val.py:176: ce / focal are accepted; the binary evaluation then refuses them as the reference's
     # binary_segmentation_loss does (ValueError "Unsupported loss_name")
-    p.add_argument("--loss", default="lovasz_hinge", choices=["bce", "lovasz_hinge", "ce", "focal"])
+    # lovasz_softmax: the multiclass evaluation reports Lovasz-softmax + Dice as its loss instead of CE + Dice
+    p.add_argument("--loss", default="lovasz_hinge", choices=["bce", "lovasz_hinge", "ce", "focal", "lovasz_softmax"])
     p.add_argument("--num-classes", default=4, type=int)
     p.add_argument("--device", default="cuda")
     p.add_argument("--input-size", default=512, type=int)
