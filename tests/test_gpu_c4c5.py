@@ -2,7 +2,7 @@
 workloads (C1: unet_plain 128x128 B=2; C4: attention_unet 512x512 B=8).
 
 The pixel tile of the narrow 1x1 kernels (psi conv forward with its BN statistics, ``attn_bwd2``)
-depends on the pixel count M (``pw_tile``, csrc/elem.hip: 2048 halved while a launch would have
+depends on the pixel count M (``pw_tile``, csrc/pointwise.hip: 2048 halved while a launch would have
 fewer than 512 blocks), so the four gates of attention_unet at 512x512 B=8 each run their own tile:
 
     gate (model/unet_attention.py:38-55)   M = 8 x H x W   Cs / Cg / Ci      tile

@@ -1,5 +1,5 @@
-"""GPU: the multitask classification head and loss glue at op level (csrc/loss.hip gap_*, linear_*,
-ce_fwd, scale_grad; losses._MultiTaskFn), which the suite otherwise sees only inside whole-model runs
+"""GPU: the multitask classification head and loss glue at op level (csrc/cls_head.hip gap_*, linear_*, ce_fwd;
+csrc/loss.hip scale_grad; losses._MultiTaskFn), which the suite otherwise sees only inside whole-model runs
 at I = 2048, O = 512 / 3.
 
 ops.cls_head (model/unet_multitask.py:73-80: GAP -> FC -> ReLU -> Dropout -> FC) against float64 torch

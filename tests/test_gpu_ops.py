@@ -345,7 +345,7 @@ def test_upsample_strided_grad(dtname, align, H, C):
 
 def _pw_head_case(dtname, K, N, H, W, C=64, preload=False, need_grad=True):
     """1x1 head conv (C -> K, bias) to fp32 NCHW logits, forward and backward.  K in {1, 2} is the
-    pw_small path, K in 3..32 the C-way pw_head kernels of csrc/multiclass.hip (whose backward needs C
+    pw_small path, K in 3..32 the C-way pw_head kernels of csrc/pointwise.hip (whose backward needs C
     to divide 256).  preload: the input node already holds a gradient (a second consumer ran first),
     so dx accumulates (dx_acc = 1); need_grad False: the input takes no gradient (dx NULL)."""
     ops, DT_BF16, DT_F32 = _ops()

@@ -15,7 +15,7 @@
 //                 one thread per output pixel, writing the collated fp32 / int64 tensors directly.
 // The resize is bit-exact with Pillow (same integer arithmetic); the HSV jitter follows OpenCV's
 // 8-bit RGB2HSV_b (integer) / HSV2RGB_b (fp32, no contraction, round-half-even) algorithm.
-#include "common.h"
+#include "elem_util.h"
 
 namespace {
 
@@ -195,10 +195,7 @@ __global__ __launch_bounds__(256) void aug_compose(const long long* desc, const 
   }
 }
 
-int grid_for(long work) {
-  long g = (work + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 1024 ? 1024 : g));
-}
+constexpr int kAugGrid = 1024;  // block cap of the loader kernels
 
 // ---- the per-sample tables built on the device (utils/augment_tables.py restated in float64) ----
 // Every float64 operation is the one numpy performs, in the same order, with contraction off, so the
@@ -354,12 +351,12 @@ UNETSEG_API int unetseg_augment_batch(const long long* desc_host, const long lon
     max_h = max_h > d[D_ROWS] * nw ? max_h : (long)(d[D_ROWS] * nw);
     max_v = max_v > nh * nw * 3 ? max_v : (long)(nh * nw * 3);
   }
-  aug_hpass<<<dim3(grid_for(max_h), B), 256, 0, stream>>>(desc, tables, src, tmp);
+  aug_hpass<<<dim3(grid_for(max_h, kAugGrid), B), 256, 0, stream>>>(desc, tables, src, tmp);
   US_LAUNCH_CHECK("aug_hpass");
-  aug_vpass<<<dim3(grid_for(max_v), B), 256, 0, stream>>>(desc, tables, tmp, rsz);
+  aug_vpass<<<dim3(grid_for(max_v, kAugGrid), B), 256, 0, stream>>>(desc, tables, tmp, rsz);
   US_LAUNCH_CHECK("aug_vpass");
-  aug_compose<<<dim3(grid_for((long)H * W), B), 256, 0, stream>>>(desc, tables, rsz, msk, H, W, num_classes, binary,
-                                                                  img, png, onehot);
+  aug_compose<<<dim3(grid_for((long)H * W, kAugGrid), B), 256, 0, stream>>>(desc, tables, rsz, msk, H, W, num_classes,
+                                                                            binary, img, png, onehot);
   US_LAUNCH_CHECK("aug_compose");
   return 0;
 }
@@ -399,14 +396,14 @@ UNETSEG_API int unetseg_augment_batch_dev(const long long* desc_host, const long
   }
   // the kernels' indices are in range by construction: every window is clamped to its image (the
   // vertical one to the row window), the nearest indices to [0, size)
-  aug_tables<<<dim3(grid_for(max_t), B), 256, 0, stream>>>(desc, hsv_r, tables);
+  aug_tables<<<dim3(grid_for(max_t, kAugGrid), B), 256, 0, stream>>>(desc, hsv_r, tables);
   US_LAUNCH_CHECK("aug_tables");
-  aug_hpass<<<dim3(grid_for(max_h), B), 256, 0, stream>>>(desc, tables, src, tmp);
+  aug_hpass<<<dim3(grid_for(max_h, kAugGrid), B), 256, 0, stream>>>(desc, tables, src, tmp);
   US_LAUNCH_CHECK("aug_hpass");
-  aug_vpass<<<dim3(grid_for(max_v), B), 256, 0, stream>>>(desc, tables, tmp, rsz);
+  aug_vpass<<<dim3(grid_for(max_v, kAugGrid), B), 256, 0, stream>>>(desc, tables, tmp, rsz);
   US_LAUNCH_CHECK("aug_vpass");
-  aug_compose<<<dim3(grid_for((long)H * W), B), 256, 0, stream>>>(desc, tables, rsz, msk, H, W, num_classes, binary,
-                                                                  img, png, onehot);
+  aug_compose<<<dim3(grid_for((long)H * W, kAugGrid), B), 256, 0, stream>>>(desc, tables, rsz, msk, H, W, num_classes,
+                                                                            binary, img, png, onehot);
   US_LAUNCH_CHECK("aug_compose");
   return 0;
 }
@@ -415,7 +412,7 @@ UNETSEG_API int unetseg_augment_batch_dev(const long long* desc_host, const long
 UNETSEG_API int unetseg_augment_tables_dev(const long long* desc, int B, const double* hsv_r, int* tables, int max_tasks,
                                            hipStream_t stream) {
   US_CHECK_ARG(B > 0 && desc && hsv_r && tables && max_tasks > 0, "augment_tables_dev: bad args");
-  aug_tables<<<dim3(grid_for(max_tasks), B), 256, 0, stream>>>(desc, hsv_r, tables);
+  aug_tables<<<dim3(grid_for(max_tasks, kAugGrid), B), 256, 0, stream>>>(desc, hsv_r, tables);
   US_LAUNCH_CHECK("aug_tables");
   return 0;
 }

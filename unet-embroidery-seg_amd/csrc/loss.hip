@@ -1,17 +1,16 @@
-// Loss, metric and optimizer kernels of the U-Net hot path.
+// Binary-segmentation loss and metric kernels of the U-Net hot path (Adam: optim.hip; the
+// classification head and its cross entropy: cls_head.hip).
 //
 //   Lovasz hinge   model/unet_training.py:219-280  (per-image sort desc, Jaccard grad, dot)
 //   BCE w/ logits  model/unet_training.py:205-216, utils/train_and_eval.py:155-182
 //   2-class->1     utils/train_and_eval.py:106-113 (z = o1 - o0, fused into the loss kernels)
-//   CE + cls head  model/unet_multitask.py:73-80,109-139
 //   confusion      utils/train_and_eval.py:116-152, train.py:330-340
-//   Adam           train.py:62-78 (torch.optim.Adam, coupled L2 weight decay)
 //
 // The Lovasz sort is a segmented, stable LSD radix sort (4 x 8-bit passes) on 32-bit keys that
 // order the hinge errors descending; ties keep ascending pixel order (the reference's
 // torch.sort is not stable, so only the loss VALUE is tie-order independent).  The sort kernels live
 // in radix_sort.h, shared with the Lovasz-softmax (lovasz_softmax.hip).
-#include "common.h"
+#include "elem_util.h"
 #include "radix_sort.h"
 
 namespace {
@@ -279,218 +278,6 @@ __global__ void confusion_kernel(const float* out, int nch, const int64_t* tgt, 
   }
 }
 
-// torch.optim.Adam single step on flat fp32 buffers (coupled L2 weight decay)
-__global__ void adam_kernel(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
-                            float eps, float wd, float bc1, float bc2_sqrt, const float* grad_scale) {
-  const float inv_scale = grad_scale ? 1.0f / grad_scale[0] : 1.0f;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    float gr = g[i] * inv_scale;
-    const float pv = p[i];
-    if (wd != 0.f) gr = gr + wd * pv;
-    float mv = m[i];
-    mv = mv + (1.f - beta1) * (gr - mv);
-    float vv = v[i] * beta2 + (1.f - beta2) * gr * gr;
-    m[i] = mv;
-    v[i] = vv;
-    const float denom = sqrtf(vv) / bc2_sqrt + eps;
-    p[i] = pv - (lr / bc1) * (mv / denom);
-  }
-}
-
-// Capturable form (hipGraph replay): lr and the step count live in device memory, so a replayed
-// step uses the current values.  hyper[0] = lr; *step is the count of steps already taken (the
-// update uses *step + 1; adam_step_commit advances it afterwards).
-__global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, long n, const float* hyper,
-                                const int* step, float beta1, float beta2, float eps, float wd,
-                                const float* grad_scale) {
-  __shared__ float k[2];
-  if (threadIdx.x == 0) {
-    const double t = (double)(step[0] + 1);
-    const double bc1 = 1.0 - pow((double)beta1, t);
-    const double bc2 = 1.0 - pow((double)beta2, t);
-    k[0] = (float)bc1;
-    k[1] = (float)sqrt(bc2);
-  }
-  __syncthreads();
-  const float bc1 = k[0], bc2_sqrt = k[1], lr = hyper[0];
-  const float inv_scale = grad_scale ? 1.0f / grad_scale[0] : 1.0f;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    float gr = g[i] * inv_scale;
-    const float pv = p[i];
-    if (wd != 0.f) gr = gr + wd * pv;
-    float mv = m[i];
-    mv = mv + (1.f - beta1) * (gr - mv);
-    float vv = v[i] * beta2 + (1.f - beta2) * gr * gr;
-    m[i] = mv;
-    v[i] = vv;
-    const float denom = sqrtf(vv) / bc2_sqrt + eps;
-    p[i] = pv - (lr / bc1) * (mv / denom);
-  }
-}
-
-__global__ void adam_step_commit_kernel(int* step) { step[0] += 1; }
-
-// ------------------------------------------------------------------------------------------
-// multitask classification head (model/unet_multitask.py:73-80)
-// ------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void gap_kernel(const T* x, int ldx, int B, int HW, int C, float* g) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * C) return;
-  const int b = i / C, c = i - b * C;
-  double s = 0.0;
-  for (int p = 0; p < HW; ++p) s += (float)x[((long)b * HW + p) * ldx + c];
-  g[i] = (float)(s / HW);
-}
-
-template <typename T>
-__global__ void gap_bwd_kernel(const float* dg, int B, int HW, int C, T* dx, int ldx, int accumulate) {
-  const long total = (long)B * HW * C;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long pix = i / C;
-    const int c = (int)(i - pix * C);
-    const int b = (int)(pix / HW);
-    T* o = dx + pix * ldx + c;
-    float v = dg[(long)b * C + c] / (float)HW;
-    if (accumulate) v += (float)(*o);
-    *o = (T)v;
-  }
-}
-
-__device__ __forceinline__ float hash_u01(unsigned long long seed, unsigned long long i) {
-  unsigned long long z = seed + (i + 1) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (float)(z >> 40) * (1.0f / 16777216.0f);
-}
-
-// y[b][o] = act(sum_i x[b][i] W[o][i] + bias[o]); act: 0 none, 1 relu, 2 relu + dropout(p)
-// one wave per output element
-__global__ void linear_fwd_kernel(const float* x, const float* W, const float* bias, int B, int I, int O, int act,
-                                  float p_drop, unsigned long long seed, const float* mask_in, float* mask_out,
-                                  float* pre, float* y) {
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-  if (wave >= B * O) return;
-  const int b = wave / O, o = wave - b * O;
-  float s = 0.f;
-  // eight rounds' loads in flight (the plain loop waited out one round trip per 64 inputs); the
-  // products are added in the same i order
-  constexpr int U = 8;
-  int i = lane;
-  for (; i + 64 * (U - 1) < I; i += 64 * U) {
-    float xv[U], wv[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      xv[u] = x[(long)b * I + i + 64 * u];
-      wv[u] = W[(long)o * I + i + 64 * u];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) s = fmaf(xv[u], wv[u], s);  // explicit: as the plain loop's contraction
-  }
-  for (; i < I; i += 64) s += x[(long)b * I + i] * W[(long)o * I + i];
-  s = wave_sum(s);
-  if (lane == 0) {
-    s += bias ? bias[o] : 0.f;
-    if (pre) pre[wave] = s;
-    if (act >= 1) s = fmaxf(s, 0.f);
-    if (act == 2) {
-      float keep;
-      if (mask_in) keep = mask_in[wave];
-      else keep = hash_u01(seed, (unsigned long long)wave) >= p_drop ? 1.f : 0.f;
-      if (mask_out) mask_out[wave] = keep;
-      s = s * keep / (1.f - p_drop);
-    }
-    y[wave] = s;
-  }
-}
-
-// backward of linear (+ act): dyp = dy * act'(pre) ; dx[b][i] = sum_o dyp W[o][i] ; dW += ; db +=
-__global__ void linear_act_bwd_kernel(const float* dy, const float* pre, const float* mask, float p_drop, int act,
-                                      int B, int O, float* dyp) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * O) return;
-  float g = dy[i];
-  if (act >= 1 && pre[i] <= 0.f) g = 0.f;
-  if (act == 2) g = g * mask[i] / (1.f - p_drop);
-  dyp[i] = g;
-}
-
-__global__ void linear_bwd_x_kernel(const float* dyp, const float* W, int B, int I, int O, float* dx) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= B * I) return;
-  const int b = t / I, i = t - b * I;
-  float s = 0.f;
-  // 32 outputs' loads in flight per round (one round trip per load left the 2048 -> 512 FC's
-  // backward at ~100 us); the products are added in the same o order as the plain loop
-  constexpr int U = 32;
-  int o = 0;
-  for (; o + U <= O; o += U) {
-    float d[U], w[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      d[u] = dyp[(long)b * O + o + u];
-      w[u] = W[(long)(o + u) * I + i];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) s = fmaf(d[u], w[u], s);  // explicit: the packed-multiply form rounds twice
-  }
-  for (; o < O; ++o) s += dyp[(long)b * O + o] * W[(long)o * I + i];
-  dx[t] = s;
-}
-
-__global__ void linear_bwd_w_kernel(const float* dyp, const float* x, int B, int I, int O, float* dW, float* db) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= O * I) return;
-  const int o = t / I, i = t - o * I;
-  float s = 0.f;
-  for (int b = 0; b < B; ++b) s += dyp[(long)b * O + o] * x[(long)b * I + i];
-  dW[t] += s;
-  if (i == 0 && db) {
-    float sb = 0.f;
-    for (int b = 0; b < B; ++b) sb += dyp[(long)b * O + o];
-    db[o] += sb;
-  }
-}
-
-// cross entropy (mean) over B rows of K logits; dlog = (softmax - onehot)/B (unscaled)
-// nn.CrossEntropyLoss() (mean, ignore_index -100): rows whose target is -100 contribute nothing and
-// the mean runs over the others; any other target outside [0, K) makes the loss and its gradient
-// NaN (torch raises; no out-of-range read here either way).
-__global__ void ce_kernel(const float* logits, const int64_t* tgt, int B, int K, float* loss, float* dlog) {
-  __shared__ double sred[16];
-  __shared__ int cnt[2];
-  if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
-  __syncthreads();
-  int nvalid = 0, nbad = 0;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    const long long t = tgt[b];
-    nvalid += (t >= 0 && t < K) ? 1 : 0;
-    nbad += (t != -100 && (t < 0 || t >= K)) ? 1 : 0;
-  }
-  atomicAdd(&cnt[0], nvalid);  // LDS atomics
-  atomicAdd(&cnt[1], nbad);
-  __syncthreads();
-  const float denom = (float)max(cnt[0], 1);
-  const bool bad = cnt[1] > 0;
-  double s = 0.0;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    const float* l = logits + (long)b * K;
-    const long long t = tgt[b];
-    const bool ok = t >= 0 && t < K;
-    float mx = l[0];
-    for (int k = 1; k < K; ++k) mx = fmaxf(mx, l[k]);
-    float se = 0.f;
-    for (int k = 0; k < K; ++k) se += expf(l[k] - mx);
-    const float lse = mx + logf(se);
-    if (ok) s += (double)(lse - l[t]);
-    for (int k = 0; k < K; ++k)
-      dlog[(long)b * K + k] = bad ? NAN : ok ? (expf(l[k] - lse) - (k == t ? 1.f : 0.f)) / denom : 0.f;
-  }
-  s = block_sum(s, sred);
-  if (threadIdx.x == 0) loss[0] = bad ? NAN : cnt[0] == 0 ? NAN : (float)(s / (double)cnt[0]);
-}
-
 // multiply a per-element gradient buffer by a device scalar: out = g * (s1[0]*a1 + s2[0]*a2)
 __global__ void scale_grad_kernel(const float* g, long n, const float* s1, float a1, const float* s2, float a2,
                                   float* out) {
@@ -498,12 +285,7 @@ __global__ void scale_grad_kernel(const float* g, long n, const float* s1, float
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = g[i] * sc;
 }
 
-inline int grid_for(long work, int cap = 8192) {
-  long b = (work + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (int)b;
-}
+constexpr int kLossGrid = 8192;  // block cap of the loss kernels (their partial buffers are sized by it)
 
 }  // namespace
 
@@ -553,8 +335,8 @@ static int lovasz_impl(const float* out, int nch, const int64_t* tgt, int B, lon
   uint32_t* hist = v1 + (long)B * P;
   uint32_t* cnt = hist + (long)B * 256 * T;
   float* part = (float*)(cnt + (long)B * T);
-  hipLaunchKernelGGL(lovasz_keygen_kernel, dim3(grid_for((long)B * P)), dim3(256), 0, st, out, nch, tgt, B, P, k0, v0,
-                     has_ignore, ignore);
+  hipLaunchKernelGGL(lovasz_keygen_kernel, dim3(grid_for((long)B * P, kLossGrid)), dim3(256), 0, st, out, nch, tgt, B,
+                     P, k0, v0, has_ignore, ignore);
   for (int pass = 0; pass < 4; ++pass) {
     const int shift = pass * 8;
     hipLaunchKernelGGL(radix_hist_kernel, dim3(T, B), dim3(256), 0, st, k0, P, T, shift, hist);
@@ -571,7 +353,9 @@ static int lovasz_impl(const float* out, int nch, const int64_t* tgt, int B, lon
   return 0;
 }
 
-UNETSEG_API size_t unetseg_bce_workspace(int B, long P) { return (size_t)grid_for((long)B * P) * sizeof(float) + 256; }
+UNETSEG_API size_t unetseg_bce_workspace(int B, long P) {
+  return (size_t)grid_for((long)B * P, kLossGrid) * sizeof(float) + 256;
+}
 
 // BCE-with-logits mean loss; gz (may be NULL) = dloss/dz (already /count); pos_weight fp32 scalar or NULL
 UNETSEG_API int unetseg_bce_fwd(const float* out, int nch, const int64_t* tgt, int B, long P, const float* pos_weight,
@@ -581,7 +365,7 @@ UNETSEG_API int unetseg_bce_fwd(const float* out, int nch, const int64_t* tgt, i
   US_CHECK_ARG(B > 0 && P > 0, "bce_fwd: empty batch");
   US_CHECK_ARG(ws_bytes >= unetseg_bce_workspace(B, P), "bce_fwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  const int G = grid_for((long)B * P);
+  const int G = grid_for((long)B * P, kLossGrid);
   hipLaunchKernelGGL(bce_kernel, dim3(G), dim3(256), 0, st, out, nch, tgt, B, P, pos_weight, gz, (float*)ws);
   hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, G, loss);
   US_LAUNCH_CHECK("bce_fwd");
@@ -593,9 +377,9 @@ UNETSEG_API int unetseg_dz_to_dout(const float* gz, int B, long P, int nch, cons
                                    float a2, float* scratch, float* dout, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const long n = (long)B * P;
-  hipLaunchKernelGGL(scale_grad_kernel, dim3(grid_for(n)), dim3(256), 0, st, gz, n, s1, a1, s2, a2, scratch);
-  hipLaunchKernelGGL(dz_to_dout_kernel, dim3(grid_for(n)), dim3(256), 0, st, scratch, B, P, nch, (const float*)nullptr,
-                     1.f, dout);
+  hipLaunchKernelGGL(scale_grad_kernel, dim3(grid_for(n, kLossGrid)), dim3(256), 0, st, gz, n, s1, a1, s2, a2, scratch);
+  hipLaunchKernelGGL(dz_to_dout_kernel, dim3(grid_for(n, kLossGrid)), dim3(256), 0, st, scratch, B, P, nch,
+                     (const float*)nullptr, 1.f, dout);
   US_LAUNCH_CHECK("dz_to_dout");
   return 0;
 }
@@ -609,97 +393,11 @@ UNETSEG_API int unetseg_confusion(const float* out, int nch, const int64_t* tgt,
   return 0;
 }
 
-UNETSEG_API int unetseg_adam(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
-                             float eps, float wd, int step, const float* grad_scale, void* stream) {
-  US_CHECK_ARG(p && g && m && v && n >= 0, "adam: null pointer or negative size");
-  US_CHECK_ARG(step >= 1, "adam: step must be >= 1");
-  const double bc1 = 1.0 - pow((double)beta1, step);
-  const double bc2 = 1.0 - pow((double)beta2, step);
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 16384)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                     beta2, eps, wd, (float)bc1, (float)sqrt(bc2), grad_scale);
-  US_LAUNCH_CHECK("adam");
-  return 0;
-}
-
-UNETSEG_API int unetseg_adam_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step,
-                                 float beta1, float beta2, float eps, float wd, const float* grad_scale,
-                                 void* stream) {
-  US_CHECK_ARG(hyper && step, "adam_dev: hyper and step must be device pointers");
-  hipLaunchKernelGGL(adam_dev_kernel, dim3(grid_for(n, 16384)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                     hyper, step, beta1, beta2, eps, wd, grad_scale);
-  hipLaunchKernelGGL(adam_step_commit_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
-  US_LAUNCH_CHECK("adam_dev");
-  return 0;
-}
-
-UNETSEG_API int unetseg_gap_fwd(int dtype, const void* x, int ldx, int B, int HW, int C, float* g, void* stream) {
-  US_CHECK_DTYPE(dtype, "gap_fwd");
-  US_CHECK_ARG(x && g && B > 0 && HW > 0 && C > 0 && ldx >= C, "gap_fwd: bad args");
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(gap_kernel<bf16>, dim3(ceil_div(B * C, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x,
-                       ldx, B, HW, C, g);
-  else
-    hipLaunchKernelGGL(gap_kernel<float>, dim3(ceil_div(B * C, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
-                       ldx, B, HW, C, g);
-  US_LAUNCH_CHECK("gap_fwd");
-  return 0;
-}
-
-UNETSEG_API int unetseg_gap_bwd(int dtype, const float* dg, int B, int HW, int C, void* dx, int ldx, int accumulate,
-                                void* stream) {
-  US_CHECK_DTYPE(dtype, "gap_bwd");
-  US_CHECK_ARG(dg && dx && B > 0 && HW > 0 && C > 0 && ldx >= C, "gap_bwd: bad args");
-  const long n = (long)B * HW * C;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(gap_bwd_kernel<bf16>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dg, B, HW, C,
-                       (bf16*)dx, ldx, accumulate);
-  else
-    hipLaunchKernelGGL(gap_bwd_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dg, B, HW, C,
-                       (float*)dx, ldx, accumulate);
-  US_LAUNCH_CHECK("gap_bwd");
-  return 0;
-}
-
-UNETSEG_API int unetseg_linear_fwd(const float* x, const float* W, const float* bias, int B, int I, int O, int act,
-                                   float p_drop, unsigned long long seed, const float* mask_in, float* mask_out,
-                                   float* pre, float* y, void* stream) {
-  US_CHECK_ARG(x && W && y && B > 0 && I > 0 && O > 0, "linear_fwd: null pointer or empty shape");
-  US_CHECK_ARG(act >= 0 && act <= 2 && (act != 2 || p_drop < 1.f), "linear_fwd: act %d / p_drop %g", act, p_drop);
-  const long threads = (long)B * O * 64;
-  hipLaunchKernelGGL(linear_fwd_kernel, dim3(ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream, x, W, bias, B,
-                     I, O, act, p_drop, seed, mask_in, mask_out, pre, y);
-  US_LAUNCH_CHECK("linear_fwd");
-  return 0;
-}
-
-// dx (may be NULL) = dyp . W ; dW += dyp^T x ; db += sum dyp ; scratch: B*O floats
-UNETSEG_API int unetseg_linear_bwd(const float* dy, const float* pre, const float* mask, float p_drop, int act,
-                                   const float* x, const float* W, int B, int I, int O, float* dx, float* dW, float* db,
-                                   float* scratch, void* stream) {
-  US_CHECK_ARG(dy && x && W && dW && db && scratch && B > 0 && I > 0 && O > 0, "linear_bwd: null pointer or empty shape");
-  US_CHECK_ARG(act >= 0 && act <= 2 && (act == 0 || pre) && (act != 2 || (mask && p_drop < 1.f)),
-               "linear_bwd: act %d needs pre (and the dropout mask)", act);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(linear_act_bwd_kernel, dim3(ceil_div(B * O, 256)), dim3(256), 0, st, dy, pre, mask, p_drop, act, B,
-                     O, scratch);
-  if (dx) hipLaunchKernelGGL(linear_bwd_x_kernel, dim3(ceil_div(B * I, 256)), dim3(256), 0, st, scratch, W, B, I, O, dx);
-  hipLaunchKernelGGL(linear_bwd_w_kernel, dim3(ceil_div(O * I, 256)), dim3(256), 0, st, scratch, x, B, I, O, dW, db);
-  US_LAUNCH_CHECK("linear_bwd");
-  return 0;
-}
-
-UNETSEG_API int unetseg_ce_fwd(const float* logits, const int64_t* tgt, int B, int K, float* loss, float* dlog,
-                               void* stream) {
-  US_CHECK_ARG(logits && tgt && loss && dlog && B > 0 && K > 0, "ce_fwd: null pointer or empty shape");
-  hipLaunchKernelGGL(ce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, tgt, B, K, loss, dlog);
-  US_LAUNCH_CHECK("ce_fwd");
-  return 0;
-}
-
 // out = g * (s1[0]*a1 + s2[0]*a2)
 UNETSEG_API int unetseg_scale_grad(const float* g, long n, const float* s1, float a1, const float* s2, float a2,
                                    float* out, void* stream) {
-  hipLaunchKernelGGL(scale_grad_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, g, n, s1, a1, s2, a2, out);
+  hipLaunchKernelGGL(scale_grad_kernel, dim3(grid_for(n, kLossGrid)), dim3(256), 0, (hipStream_t)stream, g, n, s1, a1,
+                     s2, a2, out);
   US_LAUNCH_CHECK("scale_grad");
   return 0;
 }
@@ -715,7 +413,7 @@ UNETSEG_API int unetseg_confusion_masked(const float* out, int nch, const int64_
 }
 
 UNETSEG_API size_t unetseg_masked_loss_workspace(int B, long P) {
-  return (size_t)2 * grid_for((long)B * P) * sizeof(float) + 256;
+  return (size_t)2 * grid_for((long)B * P, kLossGrid) * sizeof(float) + 256;
 }
 
 // binary loss over the non-ignored pixels; kind 0 BCE (pos_weight may be NULL), 1 Lovasz (flattened,
@@ -726,7 +424,7 @@ UNETSEG_API int unetseg_masked_loss_fwd(const float* out, int nch, const int64_t
   US_CHECK_ARG(out && tgt && gz && loss && ws && (kind == 0 || kind == 1), "masked_loss_fwd: bad args");
   US_CHECK_ARG(ws_bytes >= unetseg_masked_loss_workspace(B, P), "masked_loss_fwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  const int G = grid_for((long)B * P);
+  const int G = grid_for((long)B * P, kLossGrid);
   float* part = (float*)ws;
   float* inv = part + 2 * G;
   hipLaunchKernelGGL(masked_loss_kernel, dim3(G), dim3(256), 0, st, out, nch, tgt, B, P, ignore_index, kind, pos_weight,

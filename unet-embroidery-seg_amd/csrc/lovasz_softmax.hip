@@ -22,20 +22,12 @@
 //   partials) + 8 S (per-segment positives and weight) + 256 bytes.
 // dL/dp is written into the caller's dlogits buffer and turned into dL/dlogits in place.
 // No float atomics: every reduction has a fixed order, two runs give the same bits.
-#include "common.h"
+#include "elem_util.h"
 #include "radix_sort.h"
 
 namespace {
 
-constexpr int kMaxC = 32;                       // classes held in registers
 constexpr uint32_t kInvalidKey = 0xffffffffu;   // after desc_key(e) <= 0x7fffffff of every e >= 0
-
-inline int grid_for(long work, int cap = 8192) {
-  long b = (work + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (int)b;
-}
 
 // one pass over the logits: softmax (max-subtracted; exp and the normalisation in fp64, so the error
 // that is rounded into the 32-bit key is the correctly rounded one and near-equal errors rank as they
@@ -288,8 +280,8 @@ UNETSEG_API int unetseg_lovasz_softmax_fwd(const float* out, const int64_t* tgt,
   float* part = (float*)(cnt + (long)S * T);
   uint32_t* gseg = (uint32_t*)(part + (long)S * T);
   float* wseg = (float*)(gseg + S);
-  hipLaunchKernelGGL(lsm_keygen_kernel, dim3(grid_for((long)B * P)), dim3(256), 0, st, out, tgt, B, C, P, ignore_index,
-                     per_image, k0, v0);
+  hipLaunchKernelGGL(lsm_keygen_kernel, dim3(grid_for((long)B * P, 8192)), dim3(256), 0, st, out, tgt, B, C, P,
+                     ignore_index, per_image, k0, v0);
   for (int pass = 0; pass < 4; ++pass) {
     const int shift = pass * 8;
     hipLaunchKernelGGL(radix_hist_kernel, dim3(T, S), dim3(256), 0, st, k0, L, T, shift, hist);
@@ -306,7 +298,7 @@ UNETSEG_API int unetseg_lovasz_softmax_fwd(const float* out, const int64_t* tgt,
                      dlogits, part);
   hipLaunchKernelGGL(lsm_final_kernel, dim3(1), dim3(256), 0, st, part, wseg, S, T, loss);
   if (dlogits)
-    hipLaunchKernelGGL(lsm_jacobian_kernel, dim3(grid_for((long)B * P)), dim3(256), 0, st, out, B, C, P, dlogits);
+    hipLaunchKernelGGL(lsm_jacobian_kernel, dim3(grid_for((long)B * P, 8192)), dim3(256), 0, st, out, B, C, P, dlogits);
   US_LAUNCH_CHECK("lovasz_softmax_fwd");
   return 0;
 }

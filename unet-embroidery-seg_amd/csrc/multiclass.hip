@@ -1,115 +1,18 @@
-// Multiclass segmentation kernels: the C-way 1x1 head, the fused CE / Focal / Dice losses, the
-// multiclass confusion histogram, and predict.py's softmax -> crop -> resize -> argmax.
+// Multiclass segmentation kernels: the fused CE / Focal / Dice losses and the multiclass confusion
+// histogram.  (The C-way 1x1 head is in pointwise.hip, predict.py's softmax -> crop -> resize ->
+// argmax in tiles.hip.)
 //
 // Reference ops replaced:
-//   outc / final 1x1 (C > 2)   model/unet_resnet.py:78, model/unet_plain.py:69, model/unet_dualdense.py:88
 //   CE_Loss / Focal_Loss / Dice_loss   model/unet_training.py:9-91
 //   pixel_accuracy / mean_accuracy / mean_iou / frequency_weighted_iou   utils/train_and_eval.py:20-103
-//   softmax + cv2.resize(INTER_LINEAR) + argmax   predict.py:79-93
 //
-// Logits are fp32 planar [B][C][P] (the reference's NCHW output); activations NHWC (bf16 / fp32).
+// Logits are fp32 planar [B][C][P] (the reference's NCHW output).
 // Every reduction is two-stage (per-block partials -> one finalize block), hence deterministic.
 #include <cmath>
 
-#include "common.h"
+#include "elem_util.h"
 
 namespace {
-
-constexpr int kMaxC = 32;   // classes handled in registers
-constexpr int kHeadTile = 256;
-
-// ------------------------------------------------------------------------------------------
-// 1x1 head with K in (2, 32] outputs: y[n][k][hw] = sum_c x[p][c] w[k][c] + b[k] (fp32 out).
-// Thread per pixel, weights in LDS (broadcast reads), K accumulators in registers.
-// ------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void pw_head_fwd_kernel(const T* x, int ldx, long M, int HW, int C, int K,
-                                                          const float* w, const float* b, float* y) {
-  extern __shared__ float sw[];  // [K][C]
-  for (int i = threadIdx.x; i < K * C; i += blockDim.x) sw[i] = w[i];
-  __syncthreads();
-  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= M) return;
-  float acc[kMaxC];
-#pragma unroll
-  for (int k = 0; k < kMaxC; ++k) acc[k] = 0.f;
-  constexpr int V = 16 / sizeof(T);
-  for (int c0 = 0; c0 < C; c0 += V) {
-    float xv[V];
-    load_vec(x + p * ldx + c0, xv);
-#pragma unroll
-    for (int k = 0; k < kMaxC; ++k) {
-      if (k < K) {
-        float s = acc[k];
-#pragma unroll
-        for (int e = 0; e < V; ++e) s += xv[e] * sw[k * C + c0 + e];
-        acc[k] = s;
-      }
-    }
-  }
-  const long n = p / HW, hw = p - n * HW;
-#pragma unroll
-  for (int k = 0; k < kMaxC; ++k)
-    if (k < K) y[(n * K + k) * HW + hw] = acc[k] + (b ? b[k] : 0.f);
-}
-
-// Backward: dx (+)= dy . W (NHWC, T), dW / db partials part_w [K][C][G], part_b [K][G] over pixel
-// tiles of ppb pixels.  Thread (tx = channel, ty = pixel row); dy in planar fp32.
-template <typename T>
-__global__ __launch_bounds__(256) void pw_head_bwd_kernel(const float* dy, const T* x, int ldx, long M, int HW, int C,
-                                                          int K, const float* w, T* dx, int lddx, int dx_acc,
-                                                          float* part_w, float* part_b, int G, int ppb) {
-  extern __shared__ float sm[];  // [K][C] weights, then [256] reduction scratch
-  float* swt = sm;
-  float* red = sm + K * C;
-  for (int i = threadIdx.x; i < K * C; i += blockDim.x) swt[i] = w[i];
-  __syncthreads();
-  const int rows = blockDim.x / C;  // C divides 256 (host check)
-  const int tx = threadIdx.x % C, ty = threadIdx.x / C;
-  const long p0 = (long)blockIdx.x * ppb, p1 = min(M, p0 + ppb);
-  float sw[kMaxC], sb[kMaxC];
-#pragma unroll
-  for (int k = 0; k < kMaxC; ++k) sw[k] = sb[k] = 0.f;
-  for (long p = p0 + ty; p < p1; p += rows) {
-    const long n = p / HW, hw = p - n * HW;
-    const float xv = (float)x[p * ldx + tx];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < kMaxC; ++k) {
-      if (k < K) {
-        const float g = dy[(n * K + k) * HW + hw];
-        s += g * swt[k * C + tx];
-        sw[k] += g * xv;
-        sb[k] += g;
-      }
-    }
-    if (dx) {
-      T* dp = dx + p * lddx + tx;
-      *dp = (T)(dx_acc ? s + (float)*dp : s);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < kMaxC; ++k) {
-    if (k < K) {  // uniform
-      __syncthreads();
-      red[threadIdx.x] = sw[k];
-      __syncthreads();
-      if (ty == 0) {
-        float t = 0.f;
-        for (int r = 0; r < rows; ++r) t += red[r * C + tx];
-        part_w[((long)k * C + tx) * G + blockIdx.x] = t;
-      }
-      __syncthreads();
-      red[threadIdx.x] = sb[k];
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int r = 0; r < rows; ++r) t += red[r * C];  // column 0 threads carry the full sum
-        part_b[(long)k * G + blockIdx.x] = t;
-      }
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------------
 // Fused multiclass loss.  Per pixel i (image b, position p), logits x_c, target t:
@@ -348,57 +251,6 @@ __global__ __launch_bounds__(256) void mc_confusion_kernel(const float* out, con
     if (h[j]) atomicAdd(&hist[j], (unsigned long long)h[j]);
 }
 
-// ------------------------------------------------------------------------------------------
-// predict.py:79-93 for one image: probabilities = softmax over C of logits [C][H][W], cropped to
-// the letterbox window (y0, x0, ch, cw), resized bilinearly (half-pixel centres, edge clamp: cv2
-// INTER_LINEAR = F.interpolate(align_corners=False) without antialias) to OH x OW, argmax (first).
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void softmax_resize_argmax_kernel(const float* lg, int C, int H, int W, int y0,
-                                                                    int x0, int ch, int cw, int OH, int OW,
-                                                                    int32_t* labels) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)OH * OW) return;
-  const int oy = (int)(i / OW), ox = (int)(i - (long)oy * OW);
-  auto src = [](int d, int n_in, int n_out, int& i0, int& i1, float& l) {
-    float s = ((float)d + 0.5f) * ((float)n_in / (float)n_out) - 0.5f;
-    if (s < 0.f) s = 0.f;
-    i0 = (int)s;
-    if (i0 > n_in - 1) i0 = n_in - 1;
-    i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-    l = s - (float)i0;
-  };
-  int ya, yb, xa, xb;
-  float ly, lx;
-  src(oy, ch, OH, ya, yb, ly);
-  src(ox, cw, OW, xa, xb, lx);
-  const long HW = (long)H * W;
-  const long q[4] = {(long)(y0 + ya) * W + x0 + xa, (long)(y0 + ya) * W + x0 + xb, (long)(y0 + yb) * W + x0 + xa,
-                     (long)(y0 + yb) * W + x0 + xb};
-  const float wq[4] = {(1.f - ly) * (1.f - lx), (1.f - ly) * lx, ly * (1.f - lx), ly * lx};
-  float mx[4], den[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    float m = -INFINITY;
-    for (int c = 0; c < C; ++c) m = fmaxf(m, lg[c * HW + q[k]]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += expf(lg[c * HW + q[k]] - m);
-    mx[k] = m;
-    den[k] = s;
-  }
-  float best = -1.f;
-  int arg = 0;
-  for (int c = 0; c < C; ++c) {
-    float v = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v += wq[k] * (expf(lg[c * HW + q[k]] - mx[k]) / den[k]);
-    if (v > best) {
-      best = v;
-      arg = c;
-    }
-  }
-  labels[i] = arg;
-}
-
 inline int grid_of(long n, int per = 256, int cap = 65535 * 4) {
   long g = (n + per - 1) / per;
   if (g > cap) g = cap;
@@ -407,47 +259,6 @@ inline int grid_of(long n, int per = 256, int cap = 65535 * 4) {
 }
 
 }  // namespace
-
-#define MC_DISPATCH_T(dtype, ...) \
-  do {                            \
-    if ((dtype) == DT_BF16) {     \
-      typedef bf16 T;             \
-      __VA_ARGS__;                \
-    } else {                      \
-      typedef float T;            \
-      __VA_ARGS__;                \
-    }                             \
-  } while (0)
-
-UNETSEG_API int unetseg_pw_head_tiles(long M) { return ceil_div(M, (long)kHeadTile * 8); }
-
-UNETSEG_API int unetseg_pw_head_fwd(int dtype, const void* x, int ldx, long M, int hw, int c, int k, const float* w,
-                                    const float* b, float* y, void* stream) {
-  US_CHECK_ARG(x && w && y && k >= 1 && k <= kMaxC && c > 0 && c % (dtype == DT_BF16 ? 8 : 4) == 0,
-               "pw_head_fwd: bad args (k=%d <= %d, c=%d multiple of the 16-B vector)", k, kMaxC, c);
-  if (M <= 0) return 0;
-  const size_t lds = (size_t)k * c * sizeof(float);
-  MC_DISPATCH_T(dtype, hipLaunchKernelGGL(pw_head_fwd_kernel<T>, dim3(ceil_div(M, 256)), dim3(256), lds,
-                                          (hipStream_t)stream, (const T*)x, ldx, M, hw, c, k, w, b, y));
-  US_LAUNCH_CHECK("pw_head_fwd");
-  return 0;
-}
-
-// dx (may be NULL) (+)= dy . W ; part_w [k][c][G], part_b [k][G], G = unetseg_pw_head_tiles(M)
-UNETSEG_API int unetseg_pw_head_bwd(int dtype, const float* dy, const void* x, int ldx, long M, int hw, int c, int k,
-                                    const float* w, void* dx, int lddx, int dx_acc, float* part_w, float* part_b,
-                                    void* stream) {
-  US_CHECK_ARG(dy && x && w && part_w && part_b && k >= 1 && k <= kMaxC && c > 0 && c <= 256 && 256 % c == 0,
-               "pw_head_bwd: bad args (k=%d, c=%d must divide 256)", k, c);
-  if (M <= 0) return 0;
-  const int G = unetseg_pw_head_tiles(M);
-  const size_t lds = ((size_t)k * c + 256) * sizeof(float);
-  MC_DISPATCH_T(dtype, hipLaunchKernelGGL(pw_head_bwd_kernel<T>, dim3(G), dim3(256), lds, (hipStream_t)stream, dy,
-                                          (const T*)x, ldx, M, hw, c, k, w, (T*)dx, lddx, dx_acc, part_w, part_b, G,
-                                          kHeadTile * 8));
-  US_LAUNCH_CHECK("pw_head_bwd");
-  return 0;
-}
 
 static McArgs mc_args(const float* out, const int64_t* tgt, int B, int C, long P, const float* cls_w, long ignore,
                       int focal, float alpha, float gamma, const float* dice_t, int ct, float beta, float smooth) {
@@ -510,17 +321,5 @@ UNETSEG_API int unetseg_mc_confusion(const float* out, const int64_t* tgt, int B
   hipLaunchKernelGGL(mc_confusion_kernel, dim3(grid_of((long)B * P, 256, 2048)), dim3(256), 0, (hipStream_t)stream, out,
                      tgt, B, C, P, hist);
   US_LAUNCH_CHECK("mc_confusion");
-  return 0;
-}
-
-// labels int32 [OH][OW] for one image's logits [C][H][W] (predict.py:79-93)
-UNETSEG_API int unetseg_softmax_resize_argmax(const float* logits, int C, int H, int W, int y0, int x0, int ch, int cw,
-                                              int OH, int OW, int32_t* labels, void* stream) {
-  US_CHECK_ARG(logits && labels && C >= 1 && ch >= 1 && cw >= 1 && y0 >= 0 && x0 >= 0 && y0 + ch <= H &&
-                   x0 + cw <= W && OH >= 1 && OW >= 1,
-               "softmax_resize_argmax: bad window");
-  hipLaunchKernelGGL(softmax_resize_argmax_kernel, dim3(ceil_div((long)OH * OW, 256)), dim3(256), 0,
-                     (hipStream_t)stream, logits, C, H, W, y0, x0, ch, cw, OH, OW, labels);
-  US_LAUNCH_CHECK("softmax_resize_argmax");
   return 0;
 }

@@ -11,7 +11,7 @@
 //   i0 = (int)src, i1 = i0 + (i0 < in-1), l1 = src - i0, l0 = 1 - l1   (fp32)
 // The backward is a deterministic GATHER: every input pixel sums, in a fixed order, the output
 // pixels whose source row/column pair names it, with the forward's own weights recomputed.
-#include "common.h"
+#include "elem_util.h"
 
 namespace {
 
@@ -180,24 +180,13 @@ Axis make_axis(int in, int out, int align) {
 
 }  // namespace
 
-#define RS_DISPATCH_T(dtype, ...) \
-  do {                            \
-    if ((dtype) == DT_BF16) {     \
-      typedef bf16 T;             \
-      __VA_ARGS__;                \
-    } else {                      \
-      typedef float T;            \
-      __VA_ARGS__;                \
-    }                             \
-  } while (0)
-
 UNETSEG_API int unetseg_resize_bilinear_fwd(int dtype, const void* x, int ldx, int n, int h, int w, int c, int oh,
                                             int ow, int align_corners, void* y, int ldy, void* stream) {
   US_CHECK_ARG(x && y && n > 0 && h > 0 && w > 0 && c > 0 && oh > 0 && ow > 0 && ldx >= c && ldy >= c,
                "resize_bilinear_fwd: bad args");
   const Axis ay = make_axis(h, oh, align_corners), ax = make_axis(w, ow, align_corners);
-  RS_DISPATCH_T(dtype, hipLaunchKernelGGL(resize_fwd_kernel<T>, dim3(grid_n((long)n * oh * ow * c)), dim3(256), 0,
-                                          (hipStream_t)stream, (const T*)x, ldx, n, c, ay, ax, (T*)y, ldy));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(resize_fwd_kernel<T>, dim3(grid_n((long)n * oh * ow * c)), dim3(256), 0,
+                                       (hipStream_t)stream, (const T*)x, ldx, n, c, ay, ax, (T*)y, ldy));
   US_LAUNCH_CHECK("resize_bilinear_fwd");
   return 0;
 }
@@ -207,9 +196,9 @@ UNETSEG_API int unetseg_resize_bilinear_bwd(int dtype, const void* dy, int ldy, 
                                             void* stream) {
   US_CHECK_ARG(dy && dx && n > 0 && h > 0 && w > 0 && c > 0 && oh > 0 && ow > 0, "resize_bilinear_bwd: bad args");
   const Axis ay = make_axis(h, oh, align_corners), ax = make_axis(w, ow, align_corners);
-  RS_DISPATCH_T(dtype, hipLaunchKernelGGL(resize_bwd_kernel<T>, dim3(grid_n((long)n * h * w * c)), dim3(256), 0,
-                                          (hipStream_t)stream, (const T*)dy, ldy, n, c, ay, ax, (T*)dx, ldx,
-                                          accumulate));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(resize_bwd_kernel<T>, dim3(grid_n((long)n * h * w * c)), dim3(256), 0,
+                                       (hipStream_t)stream, (const T*)dy, ldy, n, c, ay, ax, (T*)dx, ldx,
+                                       accumulate));
   US_LAUNCH_CHECK("resize_bilinear_bwd");
   return 0;
 }
@@ -217,9 +206,9 @@ UNETSEG_API int unetseg_resize_bilinear_bwd(int dtype, const void* dy, int ldy, 
 UNETSEG_API int unetseg_pad2d_fwd(int dtype, const void* x, int ldx, int n, int h, int w, int c, int top, int left,
                                   int oh, int ow, void* y, int ldy, void* stream) {
   US_CHECK_ARG(x && y && top >= 0 && left >= 0 && top + h <= oh && left + w <= ow, "pad2d_fwd: bad args");
-  RS_DISPATCH_T(dtype, hipLaunchKernelGGL(pad_fwd_kernel<T>, dim3(grid_n((long)n * oh * ow * c)), dim3(256), 0,
-                                          (hipStream_t)stream, (const T*)x, ldx, n, h, w, c, top, left, oh, ow, (T*)y,
-                                          ldy));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(pad_fwd_kernel<T>, dim3(grid_n((long)n * oh * ow * c)), dim3(256), 0,
+                                       (hipStream_t)stream, (const T*)x, ldx, n, h, w, c, top, left, oh, ow, (T*)y,
+                                       ldy));
   US_LAUNCH_CHECK("pad2d_fwd");
   return 0;
 }
@@ -227,9 +216,9 @@ UNETSEG_API int unetseg_pad2d_fwd(int dtype, const void* x, int ldx, int n, int 
 UNETSEG_API int unetseg_pad2d_bwd(int dtype, const void* dy, int ldy, int n, int h, int w, int c, int top, int left,
                                   int oh, int ow, void* dx, int ldx, int accumulate, void* stream) {
   US_CHECK_ARG(dy && dx && top >= 0 && left >= 0 && top + h <= oh && left + w <= ow, "pad2d_bwd: bad args");
-  RS_DISPATCH_T(dtype, hipLaunchKernelGGL(pad_bwd_kernel<T>, dim3(grid_n((long)n * h * w * c)), dim3(256), 0,
-                                          (hipStream_t)stream, (const T*)dy, ldy, n, h, w, c, top, left, oh, ow,
-                                          (T*)dx, ldx, accumulate));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(pad_bwd_kernel<T>, dim3(grid_n((long)n * h * w * c)), dim3(256), 0,
+                                       (hipStream_t)stream, (const T*)dy, ldy, n, h, w, c, top, left, oh, ow,
+                                       (T*)dx, ldx, accumulate));
   US_LAUNCH_CHECK("pad2d_bwd");
   return 0;
 }
@@ -241,8 +230,8 @@ UNETSEG_API int unetseg_channel_stats(int dtype, const void* x, int ldx, long M,
                                       void* stream) {
   US_CHECK_ARG(x && part && M > 0 && c > 0 && tile > 0 && ldx >= c, "channel_stats: bad args");
   const dim3 grid(ceil_div(M, tile), ceil_div(c, 256));
-  RS_DISPATCH_T(dtype, hipLaunchKernelGGL(channel_stats_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream,
-                                          (const T*)x, ldx, M, c, tile, part));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(channel_stats_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream,
+                                       (const T*)x, ldx, M, c, tile, part));
   US_LAUNCH_CHECK("channel_stats");
   return 0;
 }

@@ -16,7 +16,64 @@
 // so a wave's loads and stores of every plane are contiguous; offsets are 64-bit.
 #include <algorithm>
 
-#include "common.h"
+#include "elem_util.h"
+
+// The letterbox path's label map (predict.predict_labels).  It stands ahead of the contraction pragma
+// below, which is for the tile kernels only: this kernel keeps the compiler's default contraction.
+namespace {
+
+// ------------------------------------------------------------------------------------------
+// predict.py:79-93 for one image: probabilities = softmax over C of logits [C][H][W], cropped to
+// the letterbox window (y0, x0, ch, cw), resized bilinearly (half-pixel centres, edge clamp: cv2
+// INTER_LINEAR = F.interpolate(align_corners=False) without antialias) to OH x OW, argmax (first).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void softmax_resize_argmax_kernel(const float* lg, int C, int H, int W, int y0,
+                                                                    int x0, int ch, int cw, int OH, int OW,
+                                                                    int32_t* labels) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)OH * OW) return;
+  const int oy = (int)(i / OW), ox = (int)(i - (long)oy * OW);
+  auto src = [](int d, int n_in, int n_out, int& i0, int& i1, float& l) {
+    float s = ((float)d + 0.5f) * ((float)n_in / (float)n_out) - 0.5f;
+    if (s < 0.f) s = 0.f;
+    i0 = (int)s;
+    if (i0 > n_in - 1) i0 = n_in - 1;
+    i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
+    l = s - (float)i0;
+  };
+  int ya, yb, xa, xb;
+  float ly, lx;
+  src(oy, ch, OH, ya, yb, ly);
+  src(ox, cw, OW, xa, xb, lx);
+  const long HW = (long)H * W;
+  const long q[4] = {(long)(y0 + ya) * W + x0 + xa, (long)(y0 + ya) * W + x0 + xb, (long)(y0 + yb) * W + x0 + xa,
+                     (long)(y0 + yb) * W + x0 + xb};
+  const float wq[4] = {(1.f - ly) * (1.f - lx), (1.f - ly) * lx, ly * (1.f - lx), ly * lx};
+  float mx[4], den[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float m = -INFINITY;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, lg[c * HW + q[k]]);
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s += expf(lg[c * HW + q[k]] - m);
+    mx[k] = m;
+    den[k] = s;
+  }
+  float best = -1.f;
+  int arg = 0;
+  for (int c = 0; c < C; ++c) {
+    float v = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v += wq[k] * (expf(lg[c * HW + q[k]] - mx[k]) / den[k]);
+    if (v > best) {
+      best = v;
+      arg = c;
+    }
+  }
+  labels[i] = arg;
+}
+
+}  // namespace
 
 // every fused multiply-add below is an explicit fmaf: the window weight is the ROUNDED product
 // w(uy) * w(ux) in the accumulation and in the normalisation alike
@@ -24,7 +81,7 @@
 
 namespace {
 
-constexpr int kTileMaxC = 32;
+constexpr int kTileMaxC = kMaxC;
 
 struct TileGrid {
   int t, o, s, nx, ny;
@@ -284,5 +341,17 @@ UNETSEG_API int unetseg_tile_finish(const float* acc, int C, int H, int W, int t
   hipLaunchKernelGGL(tile_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, acc, C, H, W, g,
                      probs, labels);
   US_LAUNCH_CHECK("tile_finish");
+  return 0;
+}
+
+// labels int32 [OH][OW] for one image's logits [C][H][W] (predict.py:79-93)
+UNETSEG_API int unetseg_softmax_resize_argmax(const float* logits, int C, int H, int W, int y0, int x0, int ch, int cw,
+                                              int OH, int OW, int32_t* labels, void* stream) {
+  US_CHECK_ARG(logits && labels && C >= 1 && ch >= 1 && cw >= 1 && y0 >= 0 && x0 >= 0 && y0 + ch <= H &&
+                   x0 + cw <= W && OH >= 1 && OW >= 1,
+               "softmax_resize_argmax: bad window");
+  hipLaunchKernelGGL(softmax_resize_argmax_kernel, dim3(ceil_div((long)OH * OW, 256)), dim3(256), 0,
+                     (hipStream_t)stream, logits, C, H, W, y0, x0, ch, cw, OH, OW, labels);
+  US_LAUNCH_CHECK("softmax_resize_argmax");
   return 0;
 }
