@@ -400,6 +400,20 @@ int unetseg_tile_accum(const float* logits, int C, int H, int W, int tile, int o
 int unetseg_tile_finish(const float* acc, int C, int H, int W, int tile, int overlap, float* probs, int32_t* labels,
                         void* stream);
 
+/* ---- flip / rotation test-time augmentation (no reference counterpart; unetseg_hip/tta.py) ----------
+ * View k in 0..7: f = k & 1, r = k >> 1; view k of x[.., H, W] is the W-flip (if f) followed by r
+ * counter-clockwise quarter turns: torch.rot90(torch.flip(x, [-1]) if f else x, r, (-2, -1)).  `views`
+ * is an 8-bit mask in 1..255 (bit k = view k), slabs ordered by ascending k, K = popcount(views).  A
+ * view with odd r (bits 2, 3, 6, 7) needs H == W.  Both calls check their arguments before any launch. */
+/* out fp32 [K][B][C][H][W] = the K views of x fp32 [B][C][H][W]; a bit-exact permutation, one launch */
+int unetseg_tta_views(const float* x, int B, int C, int H, int W, int views, float* out, void* stream);
+/* out fp32 [B][C][H][W] (identity frame) from logits fp32 [K][B][C][H][W], slab k in view k's frame:
+ * C >= 2: log(max(sum_k p_k[c] / K, FLT_MIN)), p_k the softmax over C of view k's logits at the pixel
+ * view k maps (y, x) to, summed in ascending k from 0 with fp32 adds;
+ * C == 1: log(max(mean_k sigmoid(z_k), FLT_MIN)) - log(max(mean_k sigmoid(-z_k), FLT_MIN)).
+ * 1 <= C <= 32; every output is finite. */
+int unetseg_tta_merge(const float* logits, int B, int C, int H, int W, int views, float* out, void* stream);
+
 /* ---- device augmentation of the loader (utils/hf_dataloader.py:67-105, 111-180, 183-213) -------
  * Replaces HFUnetDataset.get_random_data + preprocess + hf_unet_dataset_collate for one batch:
  * PIL BICUBIC image / NEAREST mask resize (bit-exact), flip, paste on the grey / zero canvas,

@@ -1,4 +1,4 @@
-// Shared by the memory-bound translation units (elem, pool, upsample, pointwise, resize, tiles, augment, loss,
+// Shared by the memory-bound translation units (elem, pool, upsample, pointwise, resize, tiles, tta, augment, loss,
 // lovasz_softmax, multiclass, optim, cls_head): the 16-B vector width, the dtype dispatch and the small host
 // helpers of their C-ABI sections.
 #pragma once

@@ -15,6 +15,10 @@ round-half-even of 0.3 a + 0.7 b in float32.
 instead: overlapping T x T tiles cut on the device, batched eval-mode forwards, and the per-tile
 class probabilities blended back into one map (csrc/tiles.hip, utils/tiling.py).  The default,
 ``--tile 0``, is the letterbox path above, unchanged.
+
+``--tta MODE`` (no reference counterpart) wraps the loaded model in ``unetseg_hip.tta.TTA``: every
+forward runs on the flips / quarter turns of its input and returns the log of the mean class
+probabilities (csrc/tta.hip), which both paths take as logits.  The default, ``none``, wraps nothing.
 """
 from __future__ import annotations
 
@@ -35,6 +39,7 @@ from PIL import Image  # noqa: E402
 
 from model.model_factory import SUPPORTED_MODELS, build_model  # noqa: E402
 from unetseg_hip.lib import lib  # noqa: E402
+from unetseg_hip.tta import MODES as TTA_MODES, TTA  # noqa: E402
 from utils import tiling  # noqa: E402
 from utils.hf_dataloader import RawSample, pack_batch  # noqa: E402
 from utils.utils import cvtColor, letterbox_params  # noqa: E402
@@ -200,6 +205,8 @@ def predict(args):
         raise RuntimeError("the HIP inference path needs a GPU (no CPU fallback)")
     device = torch.device("cuda")
     model = load_model(args.model, args.weights, num_classes, device)
+    if args.tta != "none":  # the letterbox input and a tile are square: every mode is valid on both paths
+        model = TTA(model, args.tta)
     if os.path.isdir(args.data_path):
         files = [str(p) for p in Path(args.data_path).rglob("*") if p.suffix in [".jpg", ".png", ".jpeg"]]
     elif os.path.isfile(args.data_path):
@@ -228,6 +235,9 @@ def parse_args(argv=None):
     p.add_argument("--overlap", default=64, type=int, help="pixels neighbouring tiles share (<= tile // 2)")
     p.add_argument("--tile-batch", default=8, type=int, help="tiles per forward")
     p.add_argument("--bf16", action="store_true", help="tiled path: run the forward under bf16 autocast")
+    p.add_argument("--tta", default="none", choices=list(TTA_MODES),
+                   help="test-time augmentation: average the class probabilities over the mirror (hflip), the "
+                        "mirror and the half turn (flips) or all eight flips and quarter turns (d4) of each input")
     return p.parse_args(argv)
 
 

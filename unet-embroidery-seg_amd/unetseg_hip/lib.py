@@ -132,6 +132,8 @@ SIGNATURES = {
     "unetseg_tile_gather": (I, [P, I, I, I, I, I, I, I, P, P]),
     "unetseg_tile_accum": (I, [P, I, I, I, I, I, I, I, P, P]),
     "unetseg_tile_finish": (I, [P, I, I, I, I, I, P, P, P]),
+    "unetseg_tta_views": (I, [P, I, I, I, I, I, P, P]),
+    "unetseg_tta_merge": (I, [P, I, I, I, I, I, P, P]),
 }
 
 #: functions returning a value rather than a status (no RuntimeError on non-zero)

@@ -6,6 +6,10 @@ IoU / Dice (eps 1e-6) plus overall and per-class classification accuracy, or for
 reference's `evaluate` (CE + Dice loss, pixel / mean accuracy, mean / frequency-weighted IoU).
 Data: the HF parquet test split (utils/hf_dataloader.py, device augmentation) or the seeded
 synthetic test split (`--data-path synthetic`, binary / multitask only).
+
+`--tta MODE` evaluates the model under flip / quarter-turn test-time augmentation
+(unetseg_hip/tta.py): the metrics and the reported loss are then computed on the merged
+log-probabilities, which stand in for the logits.
 """
 from __future__ import annotations
 
@@ -22,6 +26,7 @@ from torch.utils.data import DataLoader  # noqa: E402
 
 from model.model_factory import SUPPORTED_MODELS, build_model  # noqa: E402
 from unetseg_hip import losses  # noqa: E402
+from unetseg_hip.tta import MODES as TTA_MODES, TTA  # noqa: E402
 from utils.hf_dataloader import DeviceLoader, HFUnetDataset, make_collate  # noqa: E402
 from utils.synthetic import SyntheticSegDataset, collate  # noqa: E402
 from utils.train_and_eval import LogColor, evaluate, evaluate_binary  # noqa: E402
@@ -53,6 +58,8 @@ def val(args):
     model.load_state_dict(torch.load(args.weights, map_location="cpu", weights_only=True))
     model.to(device)
     print(f"Model loaded from: {args.weights}")
+    if args.tta != "none":  # the loops below put the wrapper, and through it the model, in eval mode
+        model = TTA(model, args.tta)
 
     if args.task == "binary":
         m = evaluate_binary(model, loader, device, loss_name=args.loss, pos_weight=None, ignore_index=None)
@@ -112,6 +119,10 @@ def parse_args(argv=None):
     p.add_argument("--batch-size", default=1, type=int)
     p.add_argument("--cache-dir", default=".hf-cache/datasets")
     p.add_argument("--synthetic-test", default=16, type=int)
+    p.add_argument("--tta", default="none", choices=list(TTA_MODES),
+                   help="test-time augmentation: average the probabilities over the mirror (hflip), the mirror and "
+                        "the half turn (flips) or all eight flips and quarter turns (d4); the reported loss is then "
+                        "computed on the merged log-probabilities, not on the model's logits")
     return p.parse_args(argv)
 
 
