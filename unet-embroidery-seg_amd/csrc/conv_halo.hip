@@ -16,15 +16,11 @@
 // Operand roles as in the TN kernels: weights = A (16 output channels per MFMA row block),
 // pixels = B, so each lane's accumulator holds 4 consecutive output channels of one pixel.
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "conv_fast.h"
 #include "fast_util.h"
-
-// halo3: order of the next tile's halo DMA (see halo3_kernel; 2 = one piece per tap step from step 0)
-#ifndef UNETSEG_HALO3_SPREAD
-#define UNETSEG_HALO3_SPREAD 2
-#endif
 
 namespace {
 
@@ -34,6 +30,51 @@ constexpr int HW_TW = 32;  // output tile width (pixels)
 // with hp & 7 (not (hp>>1) & 7 as for aligned rows): conflict-free ds_read_b128 for every start.
 __device__ __forceinline__ int swzh(int hp, int ch) { return ch ^ (hp & 7); }
 
+// ---- tile geometry shared by the kernels of this file ----
+// spatial tile sp of a launch (tiles dealt row-major within an image, images in order)
+struct Tile {
+  int nb, th, tw;  // image, tile row, tile column
+};
+__device__ __forceinline__ Tile tile_of(int sp, int tiles_w, int tiles_h) {
+  const int tw = sp % tiles_w, rest = sp / tiles_w;
+  const int th = rest % tiles_h, nb = rest / tiles_h;
+  return {nb, th, tw};
+}
+
+// A (TH + 2) x (HW_TW + 2) halo around the TH x HW_TW tile at (h0, w0).  With H % TH == 0 and
+// W % HW_TW == 0 only the halo's border pixels can leave the image, so each DMA lane keeps the
+// borders its pixel (hr, hc) lies on -- 1 top, 2 bottom, 4 left, 8 right, 16 a slot past the halo --
+// and a tile's load is one mask test against the borders that tile has outside the image.
+template <int TH>
+__device__ __forceinline__ unsigned halo_flag(int hr, int hc, bool past) {
+  return past ? 16u : (hr == 0 ? 1u : 0u) | (hr == TH + 1 ? 2u : 0u) | (hc == 0 ? 4u : 0u) | (hc == HW_TW + 1 ? 8u : 0u);
+}
+template <int TH>
+__device__ __forceinline__ unsigned halo_kill(int h0, int w0, int H, int W) {
+  return __builtin_amdgcn_readfirstlane(16u | (h0 == 0 ? 1u : 0u) | (h0 + TH >= H ? 2u : 0u) | (w0 == 0 ? 4u : 0u) |
+                                        (w0 + HW_TW >= W ? 8u : 0u));
+}
+// uniform byte offset of the halo's top-left pixel (h0 - 1, w0 - 1) of image nb, pixel pitch ldb bytes:
+// wraps below zero on the first row / column, whose lanes halo_kill sends out of range
+__device__ __forceinline__ unsigned halo_origin(int nb, int h0, int w0, int H, int W, unsigned ldb) {
+  return __builtin_amdgcn_readfirstlane((unsigned)((nb * H + h0 - 1) * W + w0 - 1) * ldb);
+}
+
+// Lane j16 + 16 kg of a wave that owns RPW rows of a tile: its pixel of the wave's 16-pixel group p
+// (two groups per row) -- row and column within the tile, and the pixel's index in an [N][OH][OW] image
+template <int RPW>
+struct LanePix {
+  int r, col;
+  __device__ __forceinline__ LanePix(int wid, int p, int j16)
+      : r(wid * RPW + p / (HW_TW / 16)), col((p % (HW_TW / 16)) * 16 + j16) {}
+  // the pixel's tap (dh, dw) in a (TH + 2) x (HW_TW + 2) halo
+  __device__ __forceinline__ int halo_px(int dh, int dw) const { return (r + 1 + dh) * (HW_TW + 2) + col + 1 + dw; }
+  // I = int where the caller's extents are known to fit 32 bits
+  template <int TH, typename I = long>
+  __device__ __forceinline__ I opix(const Tile& tl, int OH, int OW) const {
+    return ((I)tl.nb * OH + tl.th * TH + r) * OW + tl.tw * HW_TW + col;
+  }
+};
 
 // EPI: epilogue flags fixed at compile time (kEpiBias | kEpiRelu | kEpiStats | kEpiAcc), or kEpiDyn
 // to read them from the arguments; with them fixed the tile epilogue has no uniform branches and
@@ -45,7 +86,6 @@ __device__ __forceinline__ int swzh(int hp, int ch) { return ch ^ (hp & 7); }
 // channel 8b + e > 0) -- the consumer's data gradient (post 4) reads 1/16 of what the activation costs.
 constexpr int kEpiBias = 1, kEpiRelu = 2, kEpiStats = 4, kEpiAcc = 8, kEpiDyn = 16, kEpiHead1 = 32, kEpiHead2 = 64,
               kEpiMask = 128;
-
 
 // wait for half h of the HS pipeline and join the block: the vector-memory operations issued after
 // half h's DMA may stay in flight -- the next two halves (D instructions each) and the aux loads (NA)
@@ -93,9 +133,9 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
   constexpr int WCH = 9 * 64 * 8;            // 16-B chunks of resident weights
   constexpr int WI = WCH / (64 * NW);        // weight DMA instructions per wave
   static_assert(TH % NW == 0 && WCH % (64 * NW) == 0, "tile shape");
-  // the spread halo DMA issues piece i at tap step i (mode 2) or 2 i + 1 (mode 1) of the 18-step loop:
-  // every piece must land on a step that exists, or the next tile would read a partly loaded halo
-  static_assert(HI <= 18 && (HI <= 9 || UNETSEG_HALO3_SPREAD != 1), "halo pieces exceed the tap steps");
+  // the spread halo DMA issues piece i at tap step i of the 18-step loop: every piece must land on a
+  // step that exists, or the next tile would read a partly loaded halo
+  static_assert(HI <= 18, "halo pieces exceed the tap steps");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   uint4* wl = lds;                           // [9*64 rows][8 chunks]
   uint4* hl = lds + WCH;                     // [2][HP][8]
@@ -104,7 +144,6 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ntn = a.Ng >> 6;
   // block -> (output-channel tile, first spatial tile); spatial tiles dealt round-robin
   const int tn = blockIdx.x / G_per, slot = blockIdx.x % G_per;
   const int n0 = tn * 64;
@@ -112,7 +151,6 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
   const __amdgpu_buffer_rsrc_t rx = srd(a.x1, a.x1_bytes);
   const __amdgpu_buffer_rsrc_t rw = srd(a.wt, a.w_bytes);
   const __amdgpu_buffer_rsrc_t ry = srd(a.y, y_bytes);
-  (void)ntn;
   const unsigned hw_img = (unsigned)(a.OH * a.OW);
   const __amdgpu_buffer_rsrc_t rh = srd(HK ? (const void*)a.head_y : a.y,
                                         HK ? (unsigned)(a.M / (a.OH * a.OW)) * HK * hw_img * 4u : 0u);
@@ -152,8 +190,7 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
   }
 
   // ---- halo geometry of this lane's DMA slots (identical for every tile): byte offset relative to
-  // the halo's top-left pixel (swizzle included) and which border of the halo the pixel lies on --
-  // with hc % TH == 0 and wc % 32 == 0 only border pixels can leave the image, so a tile's load is
+  // the halo's top-left pixel (swizzle included) and its border flags (halo_flag), so a tile's load is
   // one add and one mask test per row ----
   unsigned hoff[HI], hflag[HI];
 #pragma unroll
@@ -161,22 +198,17 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
     const int idx = (i * NW + wid) * 64 + lane;
     const int hp = idx >> 3, hr = hp / (HW_TW + 2), hc = hp % (HW_TW + 2);
     hoff[i] = (unsigned)(hr * a.W + hc) * (unsigned)a.ldc1b + swzh(hp, lane & 7) * 16u;
-    hflag[i] = idx >= HCH ? 16u : (hr == 0 ? 1u : 0u) | (hr == TH + 1 ? 2u : 0u) | (hc == 0 ? 4u : 0u) | (hc == HW_TW + 1 ? 8u : 0u);
+    hflag[i] = halo_flag<TH>(hr, hc, idx >= HCH);
   }
   // halo DMA instructions this wave issues per tile: HI, or HI - 1 for the waves with no slot in the
   // last one (issue_halo skips it)
   const bool full_dma = HCH % (64 * NW) == 0 || ((HI - 1) * NW + wid) * 64 < HCH;
-  auto issue_halo = [&](int t, int stage) {
-    const int sp = slot + t * G_per;
-    const int tw = sp % tiles_w, rest = sp / tiles_w;
-    const int th = rest % tiles_h, nb = rest / tiles_h;
-    const int h0 = th * TH, w0 = tw * HW_TW;
+  auto issue_halo = [&](int t, int stage) {  // a whole halo at once: the first tile's
+    const Tile tl = tile_of(slot + t * G_per, tiles_w, tiles_h);
+    const int h0 = tl.th * TH, w0 = tl.tw * HW_TW;
     const unsigned base = __builtin_amdgcn_readfirstlane(lds_addr(hl + stage * HCH));
-    // origin (h0 - 1, w0 - 1) wraps below zero on the first row / column; the edge mask sends
-    // those lanes out of range
-    const unsigned hb = __builtin_amdgcn_readfirstlane((unsigned)((nb * a.H + h0 - 1) * a.W + w0 - 1) * (unsigned)a.ldc1b);
-    const unsigned kill = __builtin_amdgcn_readfirstlane(16u | (h0 == 0 ? 1u : 0u) | (h0 + TH >= a.H ? 2u : 0u) |
-                                                         (w0 == 0 ? 4u : 0u) | (w0 + HW_TW >= a.W ? 8u : 0u));
+    const unsigned hb = halo_origin(tl.nb, h0, w0, a.H, a.W, (unsigned)a.ldc1b);
+    const unsigned kill = halo_kill<TH>(h0, w0, a.H, a.W);
 #pragma unroll
     for (int i = 0; i < HI; ++i) {
       const unsigned off = (hflag[i] & kill) ? kOOB : hb + hoff[i];
@@ -190,7 +222,6 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
   constexpr int HCH2 = HP * 4;
   constexpr int HI2 = (HCH2 + 64 * NW - 1) / (64 * NW);
   constexpr int LASTW = (HCH2 - (HI2 - 1) * 64 * NW + 63) / 64;  // waves with slots in the last instruction
-  static_assert(!HS || (HCH2 % 64 != 0 || true), "");
   unsigned hoff2[HS ? HI2 : 1], hflag2[HS ? HI2 : 1];
   if constexpr (HS) {
 #pragma unroll
@@ -199,7 +230,7 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
       const int hp = idx >> 2, q = idx & 3;
       const int hr = hp / (HW_TW + 2), hc = hp % (HW_TW + 2);
       hoff2[i] = (unsigned)(hr * a.W + hc) * (unsigned)a.ldc1b + (unsigned)((q ^ (((hp >> 2) & 1) << 1)) * 16);
-      hflag2[i] = idx >= HCH2 ? 16u : (hr == 0 ? 1u : 0u) | (hr == TH + 1 ? 2u : 0u) | (hc == 0 ? 4u : 0u) | (hc == HW_TW + 1 ? 8u : 0u);
+      hflag2[i] = halo_flag<TH>(hr, hc, idx >= HCH2);
     }
   }
   const bool last_dma = wid < LASTW;  // this wave issues the last half-stage instruction
@@ -208,15 +239,11 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
   auto issue_half = [&](int h, int stage) {
     const int t = h >> 1;
     const bool live = t < my_tiles;
-    const int sp = live ? slot + t * G_per : slot;
-    const int tw = sp % tiles_w, rest = sp / tiles_w;
-    const int th = rest % tiles_h, nb = rest / tiles_h;
-    const int h0 = th * TH, w0 = tw * HW_TW;
+    const Tile tl = tile_of(live ? slot + t * G_per : slot, tiles_w, tiles_h);
+    const int h0 = tl.th * TH, w0 = tl.tw * HW_TW;
     const unsigned base = __builtin_amdgcn_readfirstlane(lds_addr(hl + stage * HCH2));
-    const unsigned hb = __builtin_amdgcn_readfirstlane((unsigned)((nb * a.H + h0 - 1) * a.W + w0 - 1) * (unsigned)a.ldc1b +
-                                                       (unsigned)(h & 1) * 64u);
-    const unsigned kill = __builtin_amdgcn_readfirstlane(16u | (h0 == 0 ? 1u : 0u) | (h0 + TH >= a.H ? 2u : 0u) |
-                                                         (w0 == 0 ? 4u : 0u) | (w0 + HW_TW >= a.W ? 8u : 0u));
+    const unsigned hb = halo_origin(tl.nb, h0, w0, a.H, a.W, (unsigned)a.ldc1b) + (unsigned)(h & 1) * 64u;
+    const unsigned kill = halo_kill<TH>(h0, w0, a.H, a.W);
 #pragma unroll
     for (int i = 0; i < HI2; ++i) {
       const unsigned off = (!live || (hflag2[i] & kill)) ? kOOB : hb + hoff2[i];
@@ -283,83 +310,55 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
       half_wait(2 * t);
       issue_half(2 * t + 3, (2 * t + 3) & 3);
     }
-    // post-op: this tile's aux values are loaded now, so their latency hides under the tap loop
+    // post-op: this tile's aux values are loaded now, so their latency hides under the tap loop: NA_
+    // loads per wave.  HS: plain loads after this half step's DMA (hs_wait counts them).  Double
+    // buffer: they go out BEFORE the next tile's DMA, as buffer loads the compiler does not track,
+    // and the epilogue waits for them with vmcnt(this wave's DMA count): waiting on loads issued
+    // after the DMA (in-order counter) retired the next tile's halo inside this tile -- the prefetch
+    // was gone (16 x 512^2 post 4: 397 us against 281 for the plain data gradient)
     uint2 zr[FC][FP];
     uint2 zb[FP];  // POST 4: the 8 mask bytes (64 channels) of this lane's pixel
-    if (!HS && POST) {
-      // double buffer: the aux loads go out BEFORE the next tile's DMA, as buffer loads the compiler
-      // does not track, and the epilogue waits for them with vmcnt(this wave's DMA count): waiting on
-      // loads issued after the DMA (in-order counter) retired the next tile's halo inside this tile --
-      // the prefetch was gone (16 x 512^2 post 4: 397 us against 281 for the plain data gradient)
-      const int sp = slot + t * G_per;
-      const int tw = sp % tiles_w, rest = sp / tiles_w;
-      const int th = rest % tiles_h, nb = rest / tiles_h;
+    if (POST) {
+      const Tile tl = tile_of(slot + t * G_per, tiles_w, tiles_h);
+      // 8 bytes at `off` of the mask bits [M][Ng/8] (POST 4) / the pre-activation aux [M][ld_aux];
+      // the buffer loads take 32-bit offsets and their arithmetic stays 32-bit (halo3_ok bounds the extents)
+      using Pix = std::conditional_t<HS, long, int>;
+      using Off = std::conditional_t<HS, long, unsigned>;
+      auto aux_load = [&](Off off) -> uint2 {
+        if constexpr (!HS) return bload64_asm(raux, off);
+        else return *reinterpret_cast<const uint2*>((POST == 4 ? (const char*)a.mbits : (const char*)a.aux) + off);
+      };
 #pragma unroll
       for (int p = 0; p < FP; ++p) {
-        const int r = wid * RPW + p / (HW_TW / 16);
-        const int col = (p % (HW_TW / 16)) * 16 + j16;
-        const unsigned opix = (unsigned)((nb * a.OH + th * TH + r) * a.OW + tw * HW_TW + col);
+        const Off opix = (Off)LanePix<RPW>(wid, p, j16).template opix<TH, Pix>(tl, a.OH, a.OW);
         if (POST == 4) {
-          zb[p] = bload64_asm(raux, opix * (unsigned)(a.Ng >> 3) + (unsigned)(n0 >> 3));
+          zb[p] = aux_load(opix * (Off)(a.Ng >> 3) + (Off)(n0 >> 3));
         } else {
 #pragma unroll
-          for (int c = 0; c < FC; ++c)
-            zr[c][p] = bload64_asm(raux, (opix * (unsigned)a.ld_aux + (unsigned)(n0 + c * 16 + kg * 4)) * 2u);
+          for (int c = 0; c < FC; ++c) zr[c][p] = aux_load((opix * (Off)a.ld_aux + (Off)(n0 + c * 16 + kg * 4)) * 2);
         }
       }
     }
     // the next tile's halo DMA, one instruction per tap step at the first HI steps of the MFMA
-    // loop below (UNETSEG_HALO3_SPREAD=2, default): issued all at once here, the eight waves spent
-    // their issue cycles together at the tile start with the MFMA pipes idle (16 x 512^2 fwd
-    // 313 -> 302-309 us, dgrad 311 -> 307-309; -DUNETSEG_HALO3_SPREAD=0 builds the old order).
-    // Mode 1 (every other step from step 1) left the last piece fewer steps to land before the
-    // tile-end wait: mode 2 measured fwd 311 -> 302 us, fwd + statistics 448 -> 433 us
+    // loop below: issued all at once here, the eight waves spent their issue cycles together at the
+    // tile start with the MFMA pipes idle (16 x 512^2 fwd 313 -> 302 us, fwd + statistics 448 -> 433 us)
+    // (the pieces are issue_halo's loop body, one per step: the same per-wave count)
     const bool dma_next = t + 1 < my_tiles;
     unsigned nx_base = 0u, nx_hb = 0u, nx_kill = 0u;
     if constexpr (!HS) {
-      if (!UNETSEG_HALO3_SPREAD) {
-        if (dma_next) issue_halo(t + 1, stage ^ 1);
-      } else if (dma_next) {
-        const int sp = slot + (t + 1) * G_per;
-        const int tw = sp % tiles_w, rest = sp / tiles_w;
-        const int th = rest % tiles_h, nb = rest / tiles_h;
-        const int h0 = th * TH, w0 = tw * HW_TW;
+      if (dma_next) {
+        const Tile tl = tile_of(slot + (t + 1) * G_per, tiles_w, tiles_h);
+        const int h0 = tl.th * TH, w0 = tl.tw * HW_TW;
         nx_base = __builtin_amdgcn_readfirstlane(lds_addr(hl + (stage ^ 1) * HCH));
-        nx_hb = __builtin_amdgcn_readfirstlane((unsigned)((nb * a.H + h0 - 1) * a.W + w0 - 1) * (unsigned)a.ldc1b);
-        nx_kill = __builtin_amdgcn_readfirstlane(16u | (h0 == 0 ? 1u : 0u) | (h0 + TH >= a.H ? 2u : 0u) |
-                                                 (w0 == 0 ? 4u : 0u) | (w0 + HW_TW >= a.W ? 8u : 0u));
+        nx_hb = halo_origin(tl.nb, h0, w0, a.H, a.W, (unsigned)a.ldc1b);
+        nx_kill = halo_kill<TH>(h0, w0, a.H, a.W);
       }
     }
     auto issue_piece = [&](int i) {
-      if (!UNETSEG_HALO3_SPREAD || !dma_next) return;
+      if (!dma_next) return;
       const unsigned off = (hflag[i] & nx_kill) ? kOOB : nx_hb + hoff[i];
       if (i < HI - 1 || HCH % (64 * NW) == 0 || hflag[i] != 16u) dma16(rx, nx_base + (unsigned)((i * NW + wid) * 1024), off);
     };
-    if (HS && POST == 4) {
-      const int sp = slot + t * G_per;
-      const int tw = sp % tiles_w, rest = sp / tiles_w;
-      const int th = rest % tiles_h, nb = rest / tiles_h;
-#pragma unroll
-      for (int p = 0; p < FP; ++p) {
-        const int r = wid * RPW + p / (HW_TW / 16);
-        const int col = (p % (HW_TW / 16)) * 16 + j16;
-        const long opix = ((long)nb * a.OH + th * TH + r) * a.OW + tw * HW_TW + col;
-        zb[p] = *reinterpret_cast<const uint2*>(a.mbits + opix * (a.Ng >> 3) + (n0 >> 3));
-      }
-    } else if (HS && POST) {
-      const int sp = slot + t * G_per;
-      const int tw = sp % tiles_w, rest = sp / tiles_w;
-      const int th = rest % tiles_h, nb = rest / tiles_h;
-#pragma unroll
-      for (int p = 0; p < FP; ++p) {
-        const int r = wid * RPW + p / (HW_TW / 16);
-        const int col = (p % (HW_TW / 16)) * 16 + j16;
-        const long opix = ((long)nb * a.OH + th * TH + r) * a.OW + tw * HW_TW + col;
-#pragma unroll
-        for (int c = 0; c < FC; ++c)
-          zr[c][p] = *reinterpret_cast<const uint2*>((const bf16*)a.aux + opix * a.ld_aux + n0 + c * 16 + kg * 4);
-      }
-    }
 #pragma unroll
     for (int c = 0; c < FC; ++c)
 #pragma unroll
@@ -387,9 +386,7 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
           }
 #pragma unroll
           for (int p = 0; p < FP; ++p) {
-            const int r = wid * RPW + p / (HW_TW / 16);
-            const int col = (p % (HW_TW / 16)) * 16 + j16;
-            const int hp = (r + 1 + dh) * (HW_TW + 2) + col + 1 + dw;
+            const int hp = LanePix<RPW>(wid, p, j16).halo_px(dh, dw);
             uint4 v = hs2[hp * 4 + (kg ^ (((hp >> 2) & 1) << 1))];
             pf[p] = *reinterpret_cast<bf16x8*>(&v);
           }
@@ -419,9 +416,7 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
         }
 #pragma unroll
         for (int p = 0; p < FP; ++p) {
-          const int r = wid * RPW + p / (HW_TW / 16);
-          const int col = (p % (HW_TW / 16)) * 16 + j16;
-          const int hp = (r + 1 + dh) * (HW_TW + 2) + col + 1 + dw;
+          const int hp = LanePix<RPW>(wid, p, j16).halo_px(dh, dw);
           uint4 v = hs[hp * 8 + swzh(hp, ch)];
           pf[p] = *reinterpret_cast<bf16x8*>(&v);
         }
@@ -437,25 +432,9 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
 #pragma unroll
           for (int p = 0; p < FP; ++p)
             acc[c][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfb[st & 1][c], pfb[st & 1][p], acc[c][p], 0, 0, 0);
-#if UNETSEG_HALO3_INTERLEAVE
-        // reads of step s+1 spread between the MFMAs of step s
-        if (st + 1 < 18) {
-#pragma unroll
-          for (int i = 0; i < FC + FP; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          }
-          __builtin_amdgcn_sched_group_barrier(0x008, FC * FP - (FC + FP), 0);
-        } else {
-          __builtin_amdgcn_sched_group_barrier(0x008, FC * FP, 0);
-        }
-#else
         if (st + 1 < 18) __builtin_amdgcn_sched_group_barrier(0x100, FC + FP, 0);  // DS reads of step st+1
         __builtin_amdgcn_sched_group_barrier(0x008, FC * FP, 0);                    // MFMAs of step st
-#endif
-        // UNETSEG_HALO3_SPREAD 1: pieces at steps 1, 3, .. 2 HI - 1; 2: at steps 0 .. HI - 1
-        if (UNETSEG_HALO3_SPREAD == 2 ? st < HI : ((st & 1) && (st >> 1) < HI))
-          issue_piece(UNETSEG_HALO3_SPREAD == 2 ? st : st >> 1);
+        if (st < HI) issue_piece(st);  // piece st of the next tile's halo
       }
     }
 
@@ -480,9 +459,7 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
         }
       }
     }
-    const int sp = slot + t * G_per;
-    const int tw = sp % tiles_w, rest = sp / tiles_w;
-    const int th = rest % tiles_h, nb = rest / tiles_h;
+    const Tile tl = tile_of(slot + t * G_per, tiles_w, tiles_h);
     float csum[FC][4];
 #pragma unroll
     for (int c = 0; c < FC; ++c)
@@ -492,9 +469,7 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
     unsigned outo[FP], mko[FP], mkx[FP], mky[FP];
 #pragma unroll
     for (int p = 0; p < FP; ++p) {
-      const int r = wid * RPW + p / (HW_TW / 16);
-      const int col = (p % (HW_TW / 16)) * 16 + j16;
-      const long opix = ((long)nb * a.OH + th * TH + r) * a.OW + tw * HW_TW + col;
+      const long opix = LanePix<RPW>(wid, p, j16).template opix<TH>(tl, a.OH, a.OW);
       outo[p] = (unsigned)(opix * a.ldy + n0) * 2u;
       mko[p] = (unsigned)(opix * (a.Ng >> 3) + (n0 >> 3));
       mkx[p] = mky[p] = 0u;
@@ -570,9 +545,8 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
       // go out of range (every wave issues exactly FP * HK head stores)
 #pragma unroll
       for (int p = 0; p < FP; ++p) {
-        const int r = wid * RPW + p / (HW_TW / 16);
-        const int col = (p % (HW_TW / 16)) * 16 + j16;
-        const unsigned pix = (unsigned)((th * TH + r) * a.OW + tw * HW_TW + col);
+        const LanePix<RPW> lp(wid, p, j16);
+        const unsigned pix = (unsigned)((tl.th * TH + lp.r) * a.OW + tl.tw * HW_TW + lp.col);  // within the image
 #pragma unroll
         for (int k = 0; k < HK; ++k) {
           float hs = 0.f;
@@ -583,7 +557,7 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
           hs += __shfl_xor(hs, 16);
           hs += __shfl_xor(hs, 32);
           hs += hbr[k];
-          bstore32(rh, kg == 0 ? ((unsigned)(nb * HK + k) * hw_img + pix) * 4u : kOOB, hs);
+          bstore32(rh, kg == 0 ? ((unsigned)(tl.nb * HK + k) * hw_img + pix) * 4u : kOOB, hs);
         }
       }
     }
@@ -649,7 +623,7 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
       // buffer stores issued by every wave (only wave 0's land), counted in the tile's closing wait:
       // as plain stores of wave 0 alone they were retired by that wait -- a full write round trip per
       // tile with the whole block parked on the barrier behind it (16 x 512^2: +140 us)
-      const unsigned so = tid < 64 ? (unsigned)(sp * 2 * a.Ng + n0 + tid) * 4u : kOOB;
+      const unsigned so = tid < 64 ? (unsigned)((slot + t * G_per) * 2 * a.Ng + n0 + tid) * 4u : kOOB;
       bstore32(rst, so, tot);
       bstore32(rst, tid < 64 ? so + (unsigned)a.Ng * 4u : kOOB, q);
     }
@@ -701,7 +675,6 @@ __global__ __launch_bounds__(64 * NW) void halo3_kernel(FastTNArgs a, int tiles_
     }
   }
 }
-
 
 // ------------------------------------------------------------------------------------------
 // The ResNet stem forward (model/resnet_backbone.py:126-131: 7x7 / stride 2 / pad 3, 3 -> 64) on the
@@ -780,13 +753,11 @@ __global__ __launch_bounds__(64 * NW) void stem_halo_kernel(const bf16* xp, unsi
     hflag[i] = idx >= HP ? 16u : (hr < 3 ? 1u : 0u) | (hr >= 2 * TH + 3 ? 2u : 0u);
   }
   auto issue_patch = [&](int t, int stage) {
-    const int sp = slot + t * G_per;
-    const int tw = sp % tiles_w, rest = sp / tiles_w;
-    const int th = rest % tiles_h, nb = rest / tiles_h;
-    const int h0 = th * TH, w0 = tw * HW_TW;
+    const Tile tl = tile_of(slot + t * G_per, tiles_w, tiles_h);
+    const int h0 = tl.th * TH, w0 = tl.tw * HW_TW;
     const unsigned base = __builtin_amdgcn_readfirstlane(lds_addr(hl + stage * HPP));
     // origin row 2*h0 - 3 wraps below zero on the first tile row; those lanes are killed
-    const unsigned hb = __builtin_amdgcn_readfirstlane((unsigned)((nb * H + 2 * h0 - 3) * Wp + 2 * w0) * 16u);
+    const unsigned hb = __builtin_amdgcn_readfirstlane((unsigned)((tl.nb * H + 2 * h0 - 3) * Wp + 2 * w0) * 16u);
     const unsigned kill = __builtin_amdgcn_readfirstlane(16u | (h0 == 0 ? 1u : 0u) | (h0 + TH >= P ? 2u : 0u));
 #pragma unroll
     for (int i = 0; i < HI; ++i) {
@@ -844,8 +815,7 @@ __global__ __launch_bounds__(64 * NW) void stem_halo_kernel(const bf16* xp, unsi
 
     // epilogue: round to bf16, BN partials of the rounded values, stores last
     const int sp = slot + t * G_per;
-    const int tw = sp % tiles_w, rest = sp / tiles_w;
-    const int th = rest % tiles_h, nb = rest / tiles_h;
+    const Tile tl = tile_of(sp, tiles_w, tiles_h);
     float csum[FC][4];
     uint2 outv[FC][FP];
     unsigned outo[FP];
@@ -857,7 +827,7 @@ __global__ __launch_bounds__(64 * NW) void stem_halo_kernel(const bf16* xp, unsi
     for (int p = 0; p < FP; ++p) {
       const int r = wid * RPW + p / (HW_TW / 16);
       const int col = (p % (HW_TW / 16)) * 16 + j16;
-      const long opix = ((long)nb * P + th * TH + r) * Q + tw * HW_TW + col;
+      const long opix = ((long)tl.nb * P + tl.th * TH + r) * Q + tl.tw * HW_TW + col;
       outo[p] = (unsigned)(opix * ldy) * 2u;
 #pragma unroll
       for (int c = 0; c < FC; ++c) {
@@ -959,7 +929,7 @@ __global__ __launch_bounds__(64 * NW) void stem_halo_kernel(const bf16* xp, unsi
 // ------------------------------------------------------------------------------------------
 // NW = 8: two waves per SIMD -- wave w owns input channels 16 (w % 4) .. of the 9 taps for output
 // channels 32 (w / 4) .. 32 (w / 4) + 31 (the X fragments are read by both halves; the single wave per
-// SIMD of NW = 4 left the MFMA pipe idle while its own LDS reads were in flight).
+// SIMD of a 4-wave block left the MFMA pipe idle while its own LDS reads were in flight).
 template <int TH, int NW>
 __global__ __launch_bounds__(64 * NW) void halo3_wgrad_kernel(HaloWgradArgs a, int tiles_w, int tiles_h, int n_sp,
                                                               int G_per) {
@@ -969,13 +939,13 @@ __global__ __launch_bounds__(64 * NW) void halo3_wgrad_kernel(HaloWgradArgs a, i
   constexpr int DI = DCH / (64 * NW);         // dY DMA instructions per wave
   constexpr int HI = (HCH + 64 * NW - 1) / (64 * NW);
   constexpr int STG = DCH + HCH;              // uint4 per stage
-  constexpr int FM = NW == 8 ? 2 : 4, FN = 9;
-  static_assert(DCH % (64 * NW) == 0, "tile shape");
+  constexpr int FM = 2, FN = 9;
+  static_assert(NW == 8 && DCH % (64 * NW) == 0, "tile shape");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wc = wid & 3, wm = NW == 8 ? wid >> 2 : 0;  // input-channel group, output-channel half
+  const int wc = wid & 3, wm = wid >> 2;  // input-channel group, output-channel half
   const int mtiles = a.Cout >> 6;
   const int grp = blockIdx.x / G_per, slot = blockIdx.x % G_per;
   const int mt = grp % mtiles, ct = grp / mtiles;
@@ -989,8 +959,7 @@ __global__ __launch_bounds__(64 * NW) void halo3_wgrad_kernel(HaloWgradArgs a, i
 
   // Lane constants of the DMA rows, so that a tile's loads cost one add (+ the halo edge test) per
   // row: the byte offset relative to the tile's first pixel (dY) / its halo's top-left pixel (X),
-  // swizzle included, and for the halo which border (top, bottom, left, right) the lane's pixel
-  // lies on -- with H % TH == 0 and W % HW_TW == 0 only border halo pixels can leave the image.
+  // swizzle included, and for the halo its border flags (halo_flag).
   const int pc = lane & 7;
   unsigned doff[DI];
 #pragma unroll
@@ -1004,23 +973,18 @@ __global__ __launch_bounds__(64 * NW) void halo3_wgrad_kernel(HaloWgradArgs a, i
     const int idx = (i * NW + wid) * 64 + lane;
     const int hp = idx >> 3, hr = hp / (HW_TW + 2), hc = hp % (HW_TW + 2);
     hoff[i] = (unsigned)(hr * a.W + hc) * ldxb + xcb + (unsigned)((pc ^ swz_tr8(hp)) * 16);
-    hflag[i] = idx >= HCH ? 16u : (hr == 0 ? 1u : 0u) | (hr == TH + 1 ? 2u : 0u) | (hc == 0 ? 4u : 0u) | (hc == HW_TW + 1 ? 8u : 0u);
+    hflag[i] = halo_flag<TH>(hr, hc, idx >= HCH);
   }
   auto issue = [&](int t, int stage) {
-    const int sp = slot + t * G_per;
-    const int tw = sp % tiles_w, rest = sp / tiles_w;
-    const int th = rest % tiles_h, nb = rest / tiles_h;
-    const int h0 = th * TH, w0 = tw * HW_TW;
+    const Tile tl = tile_of(slot + t * G_per, tiles_w, tiles_h);
+    const int h0 = tl.th * TH, w0 = tl.tw * HW_TW;
     const unsigned base = __builtin_amdgcn_readfirstlane(lds_addr(lds + stage * STG));
-    const unsigned tb = __builtin_amdgcn_readfirstlane((unsigned)((nb * a.H + h0) * a.W + w0) * (unsigned)a.ldyb);
+    const unsigned tb = __builtin_amdgcn_readfirstlane((unsigned)((tl.nb * a.H + h0) * a.W + w0) * (unsigned)a.ldyb);
 #pragma unroll
     for (int i = 0; i < DI; ++i) dma16(rdy, base + (unsigned)((i * NW + wid) * 1024), tb + doff[i]);
     const unsigned hbase = base + DCH * 16;
-    // halo origin (h0 - 1, w0 - 1): wraps below zero on the first row / column, whose lanes the
-    // edge mask sends out of range
-    const unsigned hb = __builtin_amdgcn_readfirstlane((unsigned)((nb * a.H + h0 - 1) * a.W + w0 - 1) * ldxb);
-    const unsigned kill = __builtin_amdgcn_readfirstlane(16u | (h0 == 0 ? 1u : 0u) | (h0 + TH >= a.H ? 2u : 0u) |
-                                                         (w0 == 0 ? 4u : 0u) | (w0 + HW_TW >= a.W ? 8u : 0u));
+    const unsigned hb = halo_origin(tl.nb, h0, w0, a.H, a.W, ldxb);
+    const unsigned kill = halo_kill<TH>(h0, w0, a.H, a.W);
 #pragma unroll
     for (int i = 0; i < HI; ++i) {
       const unsigned off = (hflag[i] & kill) ? kOOB : hb + hoff[i];
@@ -1100,426 +1064,48 @@ __global__ __launch_bounds__(64 * NW) void halo3_wgrad_kernel(HaloWgradArgs a, i
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// halo3r: the same convolutions with the weights resident in VGPRs instead of LDS.
-//
-// halo3_kernel keeps 72 KiB of weights in LDS, which leaves room for only two halo stages: one
-// tile's DMA (43 KiB per CU) is in flight while the current tile computes, and the counters show the
-// waves parked on that wait for a third of their cycles (SQ_WAIT_ANY 36 %, HBM at ~3.4 TB/s, MFMA
-// busy 45 % at 512^2).  Here each wave holds the weights of 32 output channels x 9 taps x 64 input
-// channels in registers (144 VGPRs, loaded once per block), which frees the LDS for THREE halo
-// stages: tile t+2 streams in while tile t computes (87 KiB in flight per CU), and the per-MFMA LDS
-// traffic drops to the pixel fragments only.
-//   waves: wid & 1 = output-channel half (32 channels, FC = 2 groups of 16); wid >> 1 = pixel set
-//   (FP = 32 / NW groups of 16 pixels of the 8 x 32 tile).
-//   Every wave issues exactly HI halo DMAs per tile (lanes past the halo load out of range into a
-//   padded stage) and, for the post-ops, exactly FC*FP aux loads, so all waits are compile-time
-//   vmcnt values: the epilogue waits for this tile's aux loads (issued before tile t+2's DMA), the
-//   end of a tile for tile t+1's halo; tile t+2's DMA stays in flight across the barrier.
-// ------------------------------------------------------------------------------------------
-
-template <int NW>
-constexpr int halo3r_stage_chunks() {
-  return ((10 * (HW_TW + 2) * 8 + 64 * NW - 1) / (64 * NW)) * 64 * NW;
-}
-
-template <int NW>
-size_t halo3r_lds_bytes() {
-  // [3 stages][padded halo] + red [NW/2][64] + bias [64] + post coefficients [4][64] + head [256][2]
-  return (size_t)3 * halo3r_stage_chunks<NW>() * 16 + (size_t)(NW / 2) * 64 * 4 + 64 * 4 + 256 * 4 + 256 * 2 * 4;
-}
-
-template <int NW, int POST, int EPI>
-__global__ __launch_bounds__(64 * NW) void halo3r_kernel(FastTNArgs a, int tiles_w, int tiles_h, int n_sp, int G_per,
-                                                         unsigned y_bytes, unsigned aux_bytes) {
-  constexpr int TH = 8;
-  constexpr bool kDyn = (EPI & kEpiDyn) != 0;
-  const bool has_bias = kDyn ? a.bias != nullptr : (EPI & kEpiBias) != 0;
-  const bool do_relu = kDyn ? a.relu != 0 : (EPI & kEpiRelu) != 0;
-  const bool do_stats = kDyn ? a.stats != nullptr : (EPI & kEpiStats) != 0;
-  const bool do_acc = kDyn ? a.accumulate != 0 : (EPI & kEpiAcc) != 0;
-  constexpr int HK = (EPI & kEpiHead2) ? 2 : (EPI & kEpiHead1) ? 1 : 0;
-  static_assert(HK == 0 || (!kDyn && POST == 0), "the fused head rides on a fixed bias + ReLU epilogue");
-  constexpr int NPG = NW / 2;                // pixel sets
-  constexpr int FP = 16 / NPG;               // 16-pixel groups per wave
-  constexpr int FC = 2;                      // 16-channel output groups per wave (32 channels)
-  constexpr int HP = (TH + 2) * (HW_TW + 2); // halo pixels
-  constexpr int HCH = HP * 8;                // 16-B chunks of a halo
-  constexpr int HI = (HCH + 64 * NW - 1) / (64 * NW);  // halo DMA instructions per wave
-  constexpr int SCH = HI * 64 * NW;          // chunks per (padded) stage
-  static_assert(SCH == halo3r_stage_chunks<NW>(), "stage size");
-  constexpr int NA = POST ? FP * FC : 0;     // aux loads per wave per tile
-  constexpr int NS = FP * FC + FP * HK;      // stores per wave per tile
-  extern __shared__ __attribute__((aligned(16))) uint4 lds[];
-  uint4* hl = lds;                                          // [3][SCH]
-  float* red = reinterpret_cast<float*>(hl + 3 * SCH);      // [NPG][64]
-  float* sbias = red + NPG * 64;                            // [64]
-  float* pco = sbias + 64;                                  // [4][64]: sc, sh, mean, inv
-  float* hred = pco + 256;                                  // [256 pixels][2]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wch = wid & 1, pg = wid >> 1;
-  const int tn = blockIdx.x / G_per, slot = blockIdx.x % G_per;
-  const int n0 = tn * 64;
-  const int my_tiles = slot < n_sp ? (n_sp - slot + G_per - 1) / G_per : 0;
-  const __amdgpu_buffer_rsrc_t rx = srd(a.x1, a.x1_bytes);
-  const __amdgpu_buffer_rsrc_t rw = srd(a.wt, a.w_bytes);
-  const __amdgpu_buffer_rsrc_t ry = srd(a.y, y_bytes);
-  const __amdgpu_buffer_rsrc_t ra = srd(POST ? a.aux : a.y, POST ? aux_bytes : 0u);
-  const unsigned hw_img = (unsigned)(a.OH * a.OW);
-  const __amdgpu_buffer_rsrc_t rh = srd(HK ? (const void*)a.head_y : a.y,
-                                        HK ? (unsigned)(a.M / (a.OH * a.OW)) * HK * hw_img * 4u : 0u);
-  const int j16 = lane & 15, kg = lane >> 4;
-
-  if (kDyn && a.bias && tid < 64) sbias[tid] = a.bias[n0 + tid];
-  if (POST == 2 && tid < 64) {
-    pco[tid] = a.psc[n0 + tid];
-    pco[64 + tid] = a.psh[n0 + tid];
-    pco[128 + tid] = a.pmean[n0 + tid];
-    pco[192 + tid] = a.pinv[n0 + tid];
-  }
-
-  // ---- resident weights: wr[jt][kk][c] = output channel n0 + 32 wch + 16 c + j16, halo tap jt,
-  // input channels 8 (4 kk + kg) .. +7 (the MFMA A fragment) ----
-  bf16x8 wr[9][2][FC];
-#pragma unroll
-  for (int jt = 0; jt < 9; ++jt) {
-    const int jr = jt / 3, js = jt - jr * 3;
-    const int wtap = (a.r0 + a.rs * jr) * a.S + (a.s0 + a.ss * js);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int c = 0; c < FC; ++c) {
-        const int k = wch * 32 + c * 16 + j16;
-        uint4 v = bload(rw, (unsigned)(n0 + k) * (unsigned)a.ldwb + (unsigned)(wtap * 128 + (kk * 4 + kg) * 16));
-        wr[jt][kk][c] = *reinterpret_cast<bf16x8*>(&v);
-      }
-  }
-  float hwr[HK > 0 ? HK : 1][FC][4], hbr[HK > 0 ? HK : 1];
-#pragma unroll
-  for (int k = 0; k < HK; ++k) {
-    hbr[k] = a.head_b[k];
-#pragma unroll
-    for (int c = 0; c < FC; ++c)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) hwr[k][c][e] = a.head_w[k * 64 + wch * 32 + c * 16 + kg * 4 + e];
-  }
-  float breg[FC][4];
-#pragma unroll
-  for (int c = 0; c < FC; ++c)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) breg[c][e] = (!kDyn && has_bias) ? a.bias[n0 + wch * 32 + c * 16 + kg * 4 + e] : 0.f;
-  // the preloads above are compiler-tracked: retire them here (a pre-existing wait the compiler
-  // accounts for), so no conservative vmcnt(0) lands inside the tile loop
-  __builtin_amdgcn_s_waitcnt(0);
-
-  // ---- halo DMA of tile t into stage t % 3 (see halo3_kernel); the lane geometry is recomputed per
-  // issue (a few VALU) rather than held in 2 x HI VGPRs; slots past the halo load out of range into
-  // the stage padding, so every wave issues exactly HI DMAs ----
-  auto issue_halo = [&](int t) {
-    const int stage = t % 3;
-    const unsigned base = __builtin_amdgcn_readfirstlane(lds_addr(hl + stage * SCH));
-    if (t >= my_tiles) {  // no such tile: the same count of DMAs, all out of range (zero fill)
-#pragma unroll
-      for (int i = 0; i < HI; ++i) dma16(rx, base + (unsigned)((i * NW + wid) * 1024), kOOB);
-      return;
-    }
-    const int sp = slot + t * G_per;
-    const int tw = sp % tiles_w, rest = sp / tiles_w;
-    const int th = rest % tiles_h, nb = rest / tiles_h;
-    const int h0 = th * TH, w0 = tw * HW_TW;
-    const unsigned hb = __builtin_amdgcn_readfirstlane((unsigned)((nb * a.H + h0 - 1) * a.W + w0 - 1) * (unsigned)a.ldc1b);
-    const unsigned kill = __builtin_amdgcn_readfirstlane(16u | (h0 == 0 ? 1u : 0u) | (h0 + TH >= a.H ? 2u : 0u) |
-                                                         (w0 == 0 ? 4u : 0u) | (w0 + HW_TW >= a.W ? 8u : 0u));
-#pragma unroll
-    for (int i = 0; i < HI; ++i) {
-      const int idx = (i * NW + wid) * 64 + lane;
-      const int hp = idx >> 3, hr = hp / (HW_TW + 2), hc = hp - hr * (HW_TW + 2);
-      const unsigned flag = idx >= HCH ? 16u : (hr == 0 ? 1u : 0u) | (hr == TH + 1 ? 2u : 0u) | (hc == 0 ? 4u : 0u) |
-                                                   (hc == HW_TW + 1 ? 8u : 0u);
-      const unsigned off = (unsigned)(hr * a.W + hc) * (unsigned)a.ldc1b + swzh(hp, lane & 7) * 16u;
-      dma16(rx, base + (unsigned)((i * NW + wid) * 1024), (flag & kill) ? kOOB : hb + off);
-    }
-  };
-
-  // this lane's pixels: group g = pg * FP + p of the tile's 16 groups (2 per row)
-  float pq0[FC][4], pq1[FC][4];
-#pragma unroll
-  for (int c = 0; c < FC; ++c)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) pq0[c][e] = pq1[c][e] = 0.f;
-  issue_halo(0);
-  issue_halo(1);
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(HI) : "memory");
-
-  // halo pixel of tap (0, 0) for each of this lane's pixel groups
-  unsigned u0[FP];
-#pragma unroll
-  for (int p = 0; p < FP; ++p) {
-    const int g = pg * FP + p;
-    u0[p] = (unsigned)(((g >> 1) + 1) * (HW_TW + 2) + (g & 1) * 16 + j16 + 1);
-  }
-  f32x4 acc[FC][FP];
-  for (int t = 0; t < my_tiles; ++t) {
-    // the tap shifts pass through an opaque copy per tile: the 9 x FP fragment addresses are then
-    // recomputed per tile (4 VALU each, beside the MFMAs) instead of being hoisted into 36 VGPRs
-    int dh0 = a.dh0, dhs = a.dhs, dw0 = a.dw0, dws = a.dws;
-    asm volatile("" : "+s"(dh0), "+s"(dhs), "+s"(dw0), "+s"(dws));
-    const int sp = slot + t * G_per;
-    const int tw = sp % tiles_w, rest = sp / tiles_w;
-    const int th = rest % tiles_h, nb = rest / tiles_h;
-    // post-op aux values of this tile: issued halfway through the tap loop (their registers live only
-    // from there) and before tile t+2's DMA, so the epilogue's wait for them leaves that DMA in flight
-    uint2 zr[FC][FP];
-    auto issue_aux = [&]() {
-#pragma unroll
-      for (int p = 0; p < FP; ++p) {
-        const int g = pg * FP + p;
-        const long opix = ((long)nb * a.OH + th * TH + (g >> 1)) * a.OW + tw * HW_TW + (g & 1) * 16 + j16;
-#pragma unroll
-        for (int c = 0; c < FC; ++c)
-          zr[c][p] = bload64_asm(ra, (unsigned)(opix * a.ld_aux + n0 + wch * 32 + c * 16 + kg * 4) * 2u);
-      }
-      issue_halo(t + 2);
-    };
-    if (!POST) issue_halo(t + 2);
-#pragma unroll
-    for (int c = 0; c < FC; ++c)
-#pragma unroll
-      for (int p = 0; p < FP; ++p) acc[c][p] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const char* hs = reinterpret_cast<const char*>(hl + (t % 3) * SCH);
-    // 18 steps (tap jt, K half kk), software-pipelined by hand: the pixel fragments of step s+1 are
-    // read before the MFMAs of step s, and sched_group_barrier pins that order (left to itself the
-    // scheduler issues each read right before its MFMAs and the waves sit on lgkmcnt)
-    // byte address of halo pixel u, chunk kg (kk 0): u * 128 + ((kg ^ u) & 7) * 16 (swzh); chunk
-    // 4 + kg (kk 1) differs in address bit 6 only
-    auto tap_addr = [&](int jt, unsigned (&ad)[FP]) {
-      const int jr = jt / 3, js = jt - jr * 3;
-      const int delta = (dh0 + dhs * jr) * (HW_TW + 2) + dw0 + dws * js;  // uniform
-#pragma unroll
-      for (int p = 0; p < FP; ++p) {
-        const unsigned u = u0[p] + (unsigned)delta;
-        ad[p] = (u << 7) | (((u ^ (unsigned)kg) & 7u) << 4);
-      }
-    };
-    auto frag_load = [&](const unsigned (&ad)[FP], int kk, bf16x8 (&pf)[FP]) {
-#pragma unroll
-      for (int p = 0; p < FP; ++p) {
-        uint4 v = *reinterpret_cast<const uint4*>(hs + (ad[p] ^ (kk ? 64u : 0u)));
-        pf[p] = *reinterpret_cast<bf16x8*>(&v);
-      }
-    };
-    unsigned ad[FP];
-    bf16x8 pfb[2][FP];
-    tap_addr(0, ad);
-    frag_load(ad, 0, pfb[0]);
-    __builtin_amdgcn_sched_group_barrier(0x100, FP, 0);  // step 0's reads form the first group
-#pragma unroll
-    for (int st = 0; st < 18; ++st) {
-      const int jt = st >> 1, kk = st & 1;
-      if (st + 1 < 18) {
-        if (kk == 1) tap_addr(jt + 1, ad);
-        frag_load(ad, (st + 1) & 1, pfb[(st + 1) & 1]);
-      }
-#pragma unroll
-      for (int c = 0; c < FC; ++c)
-#pragma unroll
-        for (int p = 0; p < FP; ++p)
-          acc[c][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[jt][kk][c], pfb[st & 1][p], acc[c][p], 0, 0, 0);
-      if (st + 1 < 18) __builtin_amdgcn_sched_group_barrier(0x100, FP, 0);  // DS reads of step st+1
-      __builtin_amdgcn_sched_group_barrier(0x008, FC * FP, 0);              // MFMAs of step st
-      if (POST && st == 8) issue_aux();
-    }
-
-    // ================= epilogue =================
-    if (POST) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(HI) : "memory");  // this tile's aux (tile t+2's halo may fly)
-#pragma unroll
-      for (int c = 0; c < FC; ++c)
-#pragma unroll
-        for (int p = 0; p < FP; ++p) asm volatile("" : "+v"(zr[c][p]));
-    }
-    float csum[FC][4];
-#pragma unroll
-    for (int c = 0; c < FC; ++c)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) csum[c][e] = 0.f;
-    uint2 outv[FC][FP];
-    unsigned outo[FP];
-#pragma unroll
-    for (int p = 0; p < FP; ++p) {
-      const int g = pg * FP + p;
-      const long opix = ((long)nb * a.OH + th * TH + (g >> 1)) * a.OW + tw * HW_TW + (g & 1) * 16 + j16;
-      outo[p] = (unsigned)(opix * a.ldy + n0) * 2u;
-#pragma unroll
-      for (int c = 0; c < FC; ++c) {
-        const int cb = wch * 32 + c * 16 + kg * 4;
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[e] = acc[c][p][e] + (!has_bias ? 0.f : kDyn ? sbias[cb + e] : breg[c][e]);
-          if (do_relu) v[e] = fmaxf(v[e], 0.f);
-        }
-        if (do_acc) {
-          const bf16* ob = reinterpret_cast<const bf16*>((const char*)a.y + outo[p] + cb * 2);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += (float)ob[e];
-        }
-        bf16 o[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          o[e] = (bf16)v[e];
-          v[e] = (float)o[e];
-        }
-        if (POST) {
-          const bf16* z = reinterpret_cast<const bf16*>(&zr[c][p]);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float zf = (float)z[e];
-            bool on = zf > 0.f;
-            float xh = 0.f;
-            if (POST == 2) {
-              const int ch = cb + e;
-              on = fmaf(zf, pco[ch], pco[64 + ch]) > 0.f;
-              xh = (zf - pco[128 + ch]) * pco[192 + ch];
-            }
-            v[e] = on ? v[e] : 0.f;
-            o[e] = (bf16)v[e];
-            pq0[c][e] += v[e];
-            if (POST == 2) pq1[c][e] += v[e] * xh;
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          csum[c][e] += v[e];
-          acc[c][p][e] = v[e];
-        }
-        outv[c][p] = *reinterpret_cast<uint2*>(o);
-      }
-    }
-    if (HK) {
-      // head logits: this wave's 32 channels per pixel (4 channel groups kg summed by shuffles); the
-      // odd-channel-half waves hand their partial sums to the even ones through LDS
-      float hsum[HK > 0 ? HK : 1][FP];
-#pragma unroll
-      for (int p = 0; p < FP; ++p)
-#pragma unroll
-        for (int k = 0; k < HK; ++k) {
-          float h = 0.f;
-#pragma unroll
-          for (int c = 0; c < FC; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) h = fmaf(acc[c][p][e], hwr[k][c][e], h);
-          h += __shfl_xor(h, 16);
-          h += __shfl_xor(h, 32);
-          hsum[k][p] = h;
-          if (wch == 1 && kg == 0) hred[((pg * FP + p) * 16 + j16) * 2 + k] = h;
-        }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#pragma unroll
-      for (int p = 0; p < FP; ++p) {
-        const int g = pg * FP + p;
-        const unsigned pix = (unsigned)((th * TH + (g >> 1)) * a.OW + tw * HW_TW + (g & 1) * 16 + j16);
-#pragma unroll
-        for (int k = 0; k < HK; ++k) {
-          const float h = hsum[k][p] + hred[(g * 16 + j16) * 2 + k] + hbr[k];
-          bstore32(rh, (wch == 0 && kg == 0) ? ((unsigned)(nb * HK + k) * hw_img + pix) * 4u : kOOB, h);
-        }
-      }
-    }
-    if (do_stats) {
-      // per-tile BN partials over the 256 pixels: column sums, then M2 about the tile mean
-#pragma unroll
-      for (int c = 0; c < FC; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float s = row16_sum(csum[c][e]);
-          if (j16 == 0) red[pg * 64 + wch * 32 + c * 16 + kg * 4 + e] = s;
-        }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      float qv[FC][4];
-#pragma unroll
-      for (int c = 0; c < FC; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int col = wch * 32 + c * 16 + kg * 4 + e;
-          float tot = 0.f;
-#pragma unroll
-          for (int w = 0; w < NPG; ++w) tot += red[w * 64 + col];
-          const float mean = tot * (1.0f / (TH * HW_TW));
-          float q = 0.f;
-#pragma unroll
-          for (int p = 0; p < FP; ++p) {
-            const float d = acc[c][p][e] - mean;
-            q += d * d;
-          }
-          qv[c][e] = row16_sum(q);
-        }
-      float stot = 0.f;
-      if (tid < 64)
-#pragma unroll
-        for (int w = 0; w < NPG; ++w) stot += red[w * 64 + tid];
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#pragma unroll
-      for (int c = 0; c < FC; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (j16 == 0) red[pg * 64 + wch * 32 + c * 16 + kg * 4 + e] = qv[c][e];
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      if (tid < 64) {
-        float q = 0.f;
-#pragma unroll
-        for (int w = 0; w < NPG; ++w) q += red[w * 64 + tid];
-        a.stats[(long)sp * 2 * a.Ng + n0 + tid] = stot;
-        a.stats[(long)sp * 2 * a.Ng + a.Ng + n0 + tid] = q;
-      }
-    }
-#pragma unroll
-    for (int p = 0; p < FP; ++p)
-#pragma unroll
-      for (int c = 0; c < FC; ++c) bstore64(ry, outo[p] + (wch * 32 + c * 16 + kg * 4) * 2, outv[c][p]);
-    // tile t+1's halo landed: after it this wave issued tile t-1's stores, tile t's aux loads, tile
-    // t+2's DMA and tile t's stores (compiler-visible stats stores only add to the wait); the
-    // barrier also frees stage t % 3 for tile t+3's DMA, `red` and `hred`
-    constexpr int kEnd = NS + NA + HI + NS;  // vmcnt holds 6 bits: a smaller count only waits longer
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(kEnd < 63 ? kEnd : 63) : "memory");
-  }
-  // the zero-fill DMAs of the last two (absent) tiles may still be landing in the stages
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-  if (POST) {
-    float* pr = reinterpret_cast<float*>(hl);  // [NW][2][64]
-#pragma unroll
-    for (int c = 0; c < FC; ++c)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float t0 = row16_sum(pq0[c][e]), t1 = POST == 2 ? row16_sum(pq1[c][e]) : 0.f;
-        if (j16 == 0) {
-          const int col = wch * 32 + c * 16 + kg * 4 + e;
-          pr[(pg * 2 + 0) * 64 + col] = t0;
-          pr[(pg * 2 + 1) * 64 + col] = t1;
-        }
-      }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (tid < 128) {
-      const int k = tid >> 6, ch = tid & 63;
-      float t = 0.f;
-#pragma unroll
-      for (int w = 0; w < NPG; ++w) t += pr[(w * 2 + k) * 64 + ch];
-      a.ppart[(long)blockIdx.x * 2 * a.Ng + k * a.Ng + n0 + ch] = t;
-    }
-  }
-}
-
 template <int TH, int NW>
-size_t halo_lds_bytes(int head_k = 0) {
-  (void)head_k;
+size_t halo_lds_bytes() {
   return (size_t)9 * 64 * 128 + 2 * (size_t)(TH + 2) * (HW_TW + 2) * 128 + NW * 64 * 4 + 64 * 4;
+}
+
+constexpr int kHalo3TH = 8, kHalo3NW = 8;  // tile rows and waves of every halo3_kernel launch
+constexpr int kWgradTH = 8;                 // tile rows of halo3_wgrad_kernel
+
+// the TH x HW_TW spatial tiles of n_img images of h x w pixels
+struct HaloTiles {
+  int tiles_w, tiles_h, n_sp;
+};
+HaloTiles halo_tiles(int n_img, int h, int w, int TH) {
+  const int tiles_w = w / HW_TW, tiles_h = h / TH;
+  return {tiles_w, tiles_h, n_img * tiles_h * tiles_w};
+}
+
+// grid of a halo3 launch: ntn output-channel tiles x G_per persistent blocks each, about one block per
+// CU in all, which walk the n_sp spatial tiles
+struct HaloGrid {
+  int tiles_w, tiles_h, n_sp, ntn, G_per;
+};
+HaloGrid halo_grid(const FastTNArgs& a, int TH) {
+  const HaloTiles t = halo_tiles(a.M / (a.hc * a.wc), a.hc, a.wc, TH);
+  const int ntn = a.Ng / 64;
+  int G_per = 256 / ntn;
+  if (G_per < 1) G_per = 1;
+  if (G_per > t.n_sp) G_per = t.n_sp;
+  return {t.tiles_w, t.tiles_h, t.n_sp, ntn, G_per};
+}
+
+// raise kernel K's dynamic LDS limit to `bytes`, once per instantiation
+template <auto K>
+void allow_lds(size_t bytes) {
+  static const hipError_t once =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  (void)once;
 }
 
 }  // namespace
 
-int halo_tile_m() { return 8 * HW_TW; }
+int halo_tile_m() { return kHalo3TH * HW_TW; }
 
 bool halo3_ok(const FastTNArgs& a) {
   static const bool off = getenv("UNETSEG_NO_HALO") != nullptr;
@@ -1529,149 +1115,73 @@ bool halo3_ok(const FastTNArgs& a) {
   const int dh_lo = a.dhs > 0 ? a.dh0 : a.dh0 - 2, dw_lo = a.dws > 0 ? a.dw0 : a.dw0 - 2;
   if (dh_lo != -1 || dw_lo != -1) return false;  // halo of one pixel on every side
   if (a.ostride != 1 || a.ph || a.pw || a.OH != a.hc || a.OW != a.wc || a.H != a.hc || a.W != a.wc) return false;
-  if (a.Ng % 64 || a.hc % 8 || a.wc % HW_TW) return false;
+  if (a.Ng % 64 || a.hc % kHalo3TH || a.wc % HW_TW) return false;
   if ((long)a.M * a.ldy * 2 >= (1L << 31)) return false;
   if (a.post && a.post != 4 && (long)a.M * a.ld_aux * 2 >= (1L << 31)) return false;
   if (a.post == 4 && (long)a.M * (a.Ng >> 3) >= (1L << 31)) return false;
   return true;
 }
 
-template <int TH, int NW, int POST, int EPI, bool HS>
+template <int POST, int EPI, bool HS>
 static int launch_halo3_hs(const FastTNArgs& a, hipStream_t st) {
-  const int tiles_w = a.wc / HW_TW, tiles_h = a.hc / TH;
-  const int n_img = a.M / (a.hc * a.wc);
-  const int n_sp = n_img * tiles_h * tiles_w;
-  const int ntn = a.Ng / 64;
-  int G_per = 256 / ntn;
-  if (G_per < 1) G_per = 1;
-  if (G_per > n_sp) G_per = n_sp;
-  constexpr int HK = (EPI & kEpiHead2) ? 2 : (EPI & kEpiHead1) ? 1 : 0;
-  const size_t lds = halo_lds_bytes<TH, NW>(HK);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&halo3_kernel<TH, NW, POST, EPI, HS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
-  // experiment (UNETSEG_HALO_EXP_NOSTORE=1, wrong results): a zero-extent output descriptor -- the
-  // output stores still issue (the vmcnt bookkeeping is unchanged) but the hardware drops them, so the
-  // launch time without the output's HBM writes can be measured
-  static const bool nostore = getenv("UNETSEG_HALO_EXP_NOSTORE") != nullptr;
-  const unsigned y_bytes = nostore ? 0u : (unsigned)((long)a.M * a.ldy * 2);
-  hipLaunchKernelGGL((halo3_kernel<TH, NW, POST, EPI, HS>), dim3(ntn * G_per), dim3(64 * NW), lds, st, a, tiles_w, tiles_h,
-                     n_sp, G_per, y_bytes);
+  constexpr int TH = kHalo3TH, NW = kHalo3NW;
+  const HaloGrid g = halo_grid(a, TH);
+  const size_t lds = halo_lds_bytes<TH, NW>();
+  allow_lds<&halo3_kernel<TH, NW, POST, EPI, HS>>(lds);
+  const unsigned y_bytes = (unsigned)((long)a.M * a.ldy * 2);
+  hipLaunchKernelGGL((halo3_kernel<TH, NW, POST, EPI, HS>), dim3(g.ntn * g.G_per), dim3(64 * NW), lds, st, a, g.tiles_w,
+                     g.tiles_h, g.n_sp, g.G_per, y_bytes);
   return 0;
 }
 
-// The half-stage pipeline (HS) for the 8-wave kernels (UNETSEG_HALO_HS=1; default: the whole-tile
-// double buffer; read per call, the parity tests run both).  Isolated, a 512^2 layer (64 tiles per
+// The half-stage pipeline (HS) (UNETSEG_HALO_HS=1; default: the whole-tile double buffer; read per
+// call, the parity tests run both).  Isolated, a 512^2 layer (64 tiles per
 // block) is slower with it (fwd 349-363 vs 296-312 us: a second barrier per tile) and a 256^2 one
 // faster (104.8 vs 124.6 us: the three-half prologue hides the first tile's load).  Round 4 (eager
 // host) measured HS everywhere best in the step (C2 972.8 vs 962.1 img/s); with the replayed step plan
 // of round 5 the double buffer is (C2 1016-1019 vs 1010-1011 on one box, 958-959 vs 957 on another).
-template <int TH, int NW, int POST, int EPI>
+template <int POST, int EPI>
 static int launch_halo3_cfg(const FastTNArgs& a, hipStream_t st) {
   const char* e = getenv("UNETSEG_HALO_HS");
   const bool hs = e != nullptr && atoi(e) != 0;
-  if constexpr (NW == 8) {
-    if (hs) return launch_halo3_hs<TH, NW, POST, EPI, true>(a, st);
-  }
-  return launch_halo3_hs<TH, NW, POST, EPI, false>(a, st);
+  if (hs) return launch_halo3_hs<POST, EPI, true>(a, st);
+  return launch_halo3_hs<POST, EPI, false>(a, st);
 }
 
 // blocks (= post-op partial rows) of a launch_halo3 call
 int halo3_blocks(const FastTNArgs& a) {
-  const int n_sp = (a.M / (a.hc * a.wc)) * (a.hc / 8) * (a.wc / HW_TW);
-  const int ntn = a.Ng / 64;
-  int G_per = 256 / ntn;
-  if (G_per < 1) G_per = 1;
-  if (G_per > n_sp) G_per = n_sp;
-  return ntn * G_per;
-}
-
-template <int NW, int POST, int EPI>
-static int launch_halo3r_cfg(const FastTNArgs& a, hipStream_t st) {
-  constexpr int TH = 8;
-  const int tiles_w = a.wc / HW_TW, tiles_h = a.hc / TH;
-  const int n_img = a.M / (a.hc * a.wc);
-  const int n_sp = n_img * tiles_h * tiles_w;
-  const int ntn = a.Ng / 64;
-  int G_per = 256 / ntn;
-  if (G_per < 1) G_per = 1;
-  if (G_per > n_sp) G_per = n_sp;
-  const size_t lds = halo3r_lds_bytes<NW>();
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&halo3r_kernel<NW, POST, EPI>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
-  const unsigned y_bytes = (unsigned)((long)a.M * a.ldy * 2);
-  const long aux_bytes = POST ? (long)a.M * a.ld_aux * 2 : 0;
-  if (aux_bytes >= (1L << 31)) return -1;
-  hipLaunchKernelGGL((halo3r_kernel<NW, POST, EPI>), dim3(ntn * G_per), dim3(64 * NW), lds, st, a, tiles_w, tiles_h,
-                     n_sp, G_per, y_bytes, (unsigned)aux_bytes);
-  return 0;
-}
-
-template <int NW>
-static int launch_halo3r(const FastTNArgs& a, int epi, bool dyn, hipStream_t st) {
-  if (a.head_y) {
-    if (a.post || epi != (kEpiBias | kEpiRelu) || (a.head_k != 1 && a.head_k != 2)) return -1;
-    return a.head_k == 2 ? launch_halo3r_cfg<NW, 0, kEpiBias | kEpiRelu | kEpiHead2>(a, st)
-                         : launch_halo3r_cfg<NW, 0, kEpiBias | kEpiRelu | kEpiHead1>(a, st);
-  }
-  if (a.post == 1) return epi == 0 && !dyn ? launch_halo3r_cfg<NW, 1, 0>(a, st) : launch_halo3r_cfg<NW, 1, kEpiDyn>(a, st);
-  if (a.post == 2) return epi == 0 && !dyn ? launch_halo3r_cfg<NW, 2, 0>(a, st) : launch_halo3r_cfg<NW, 2, kEpiDyn>(a, st);
-  if (!dyn) switch (epi) {
-      case kEpiBias | kEpiRelu: return launch_halo3r_cfg<NW, 0, kEpiBias | kEpiRelu>(a, st);
-      case kEpiStats: return launch_halo3r_cfg<NW, 0, kEpiStats>(a, st);
-      case 0: return launch_halo3r_cfg<NW, 0, 0>(a, st);
-      case kEpiAcc: return launch_halo3r_cfg<NW, 0, kEpiAcc>(a, st);
-      default: break;
-    }
-  return launch_halo3r_cfg<NW, 0, kEpiDyn>(a, st);
+  const HaloGrid g = halo_grid(a, kHalo3TH);
+  return g.ntn * g.G_per;
 }
 
 int launch_halo3(const FastTNArgs& a, hipStream_t st) {
-  // UNETSEG_HALO_R=1: the register-resident-weight kernel (UNETSEG_HALO_R_NW=4: one wave per SIMD)
-  static const bool v1 = getenv("UNETSEG_HALO_R") == nullptr;
-  static const int rnw = getenv("UNETSEG_HALO_R_NW") ? atoi(getenv("UNETSEG_HALO_R_NW")) : 8;
-  if (!v1) {
-    static const bool dyn_r = getenv("UNETSEG_HALO_EPI_DYN") != nullptr;
-    const int epi_r = (a.bias ? kEpiBias : 0) | (a.relu ? kEpiRelu : 0) | (a.stats ? kEpiStats : 0) |
-                      (a.accumulate ? kEpiAcc : 0);
-    return rnw == 4 ? launch_halo3r<4>(a, epi_r, dyn_r, st) : launch_halo3r<8>(a, epi_r, dyn_r, st);
-  }
-  static const int nw = getenv("UNETSEG_HALO_W4") ? 4 : 8;
   // fused dgrad post-ops are separate instantiations: their registers must not cost the plain path
-  static const bool dyn = getenv("UNETSEG_HALO_EPI_DYN") != nullptr;
   const int epi = (a.bias ? kEpiBias : 0) | (a.relu ? kEpiRelu : 0) | (a.stats ? kEpiStats : 0) |
                   (a.accumulate ? kEpiAcc : 0);
   if (a.head_y) {  // fused head: bias + ReLU epilogue only (checked by the caller)
     if (a.post || epi != (kEpiBias | kEpiRelu) || (a.head_k != 1 && a.head_k != 2)) return -1;
-    return a.head_k == 2 ? launch_halo3_cfg<8, 8, 0, kEpiBias | kEpiRelu | kEpiHead2>(a, st)
-                         : launch_halo3_cfg<8, 8, 0, kEpiBias | kEpiRelu | kEpiHead1>(a, st);
+    return a.head_k == 2 ? launch_halo3_cfg<0, kEpiBias | kEpiRelu | kEpiHead2>(a, st)
+                         : launch_halo3_cfg<0, kEpiBias | kEpiRelu | kEpiHead1>(a, st);
   }
   if (a.mbits_out) {  // ReLU mask bits: bias + ReLU epilogue only (checked by the caller)
     if (a.post || epi != (kEpiBias | kEpiRelu)) return -1;
-    return launch_halo3_cfg<8, 8, 0, kEpiBias | kEpiRelu | kEpiMask>(a, st);
+    return launch_halo3_cfg<0, kEpiBias | kEpiRelu | kEpiMask>(a, st);
   }
-  if (a.post == 4) return epi == 0 ? launch_halo3_cfg<8, 8, 4, 0>(a, st) : -1;
-  // fused dgrad post-ops come with a plain epilogue (no bias / ReLU / stats / accumulate)
-  if (a.post == 1) return epi == 0 && !dyn ? launch_halo3_cfg<8, 8, 1, 0>(a, st) : launch_halo3_cfg<8, 8, 1, kEpiDyn>(a, st);
-  if (a.post == 2) return epi == 0 && !dyn ? launch_halo3_cfg<8, 8, 2, 0>(a, st) : launch_halo3_cfg<8, 8, 2, kEpiDyn>(a, st);
-  if (nw == 4) return launch_halo3_cfg<8, 4, 0, kEpiDyn>(a, st);
+  if (a.post == 4) return epi == 0 ? launch_halo3_cfg<4, 0>(a, st) : -1;
+  // fused dgrad post-ops come with a plain epilogue (no bias / ReLU / stats / accumulate): the C ABI's
+  // post-op data gradient always plans with none of them, so no call reaches the kEpiDyn fallbacks of
+  // post 1 / 2 today (compiled, untested)
+  if (a.post == 1) return epi == 0 ? launch_halo3_cfg<1, 0>(a, st) : launch_halo3_cfg<1, kEpiDyn>(a, st);
+  if (a.post == 2) return epi == 0 ? launch_halo3_cfg<2, 0>(a, st) : launch_halo3_cfg<2, kEpiDyn>(a, st);
   // the epilogues the U-Net runs: conv+bias+ReLU (decoder), conv with BN statistics (encoder),
-  // plain data gradient, accumulated data gradient
-  if (!dyn) switch (epi) {
-      case kEpiBias | kEpiRelu: return launch_halo3_cfg<8, 8, 0, kEpiBias | kEpiRelu>(a, st);
-      case kEpiStats: return launch_halo3_cfg<8, 8, 0, kEpiStats>(a, st);
-      case 0: return launch_halo3_cfg<8, 8, 0, 0>(a, st);
-      case kEpiAcc: return launch_halo3_cfg<8, 8, 0, kEpiAcc>(a, st);
-      default: break;
-    }
-  return launch_halo3_cfg<8, 8, 0, kEpiDyn>(a, st);
+  // plain data gradient, accumulated data gradient; any other combination reads its flags at run time
+  switch (epi) {
+    case kEpiBias | kEpiRelu: return launch_halo3_cfg<0, kEpiBias | kEpiRelu>(a, st);
+    case kEpiStats: return launch_halo3_cfg<0, kEpiStats>(a, st);
+    case 0: return launch_halo3_cfg<0, 0>(a, st);
+    case kEpiAcc: return launch_halo3_cfg<0, kEpiAcc>(a, st);
+    default: return launch_halo3_cfg<0, kEpiDyn>(a, st);
+  }
 }
 
 // the stem forward on stem_halo_kernel: 64 output channels, even input sizes with P % 16 == 0 and
@@ -1695,12 +1205,7 @@ int launch_stem_halo(const void* xp, int n, int h, int w, const void* wk, void* 
   const int blocks = n_sp < 256 ? n_sp : 256;
   constexpr int HPP = (kStemPR * kStemPC + 64 * NW - 1) / (64 * NW) * (64 * NW);
   const size_t lds = (size_t)7 * 64 * 128 + (size_t)NST * HPP * 16 + NW * 64 * 4;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_halo_kernel<NW, NST>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
+  allow_lds<&stem_halo_kernel<NW, NST>>(lds);
   hipLaunchKernelGGL((stem_halo_kernel<NW, NST>), dim3(blocks), dim3(64 * NW), lds, st, (const bf16*)xp,
                      (unsigned)((long)n * h * Wp * 16), (const bf16*)wk, h, Wp, P, Q, n_sp, (bf16*)y, ldy,
                      (unsigned)((long)n * P * Q * ldy * 2), stats);
@@ -1710,7 +1215,7 @@ int launch_stem_halo(const void* xp, int n, int h, int w, const void* wk, void* 
 bool halo3_wgrad_ok(const HaloWgradArgs& a) {
   static const bool off = getenv("UNETSEG_NO_HALO") != nullptr;
   if (off) return false;
-  return a.cin % 64 == 0 && a.c1 % 64 == 0 && a.Cout % 64 == 0 && a.H % 8 == 0 && a.W % HW_TW == 0;
+  return a.cin % 64 == 0 && a.c1 % 64 == 0 && a.Cout % 64 == 0 && a.H % kWgradTH == 0 && a.W % HW_TW == 0;
 }
 
 // Blocks per (cout, cin) group: one persistent block per CU at a time (152 KiB LDS), so the
@@ -1719,7 +1224,7 @@ bool halo3_wgrad_ok(const HaloWgradArgs& a) {
 // A/B against the 4-wave kernel's 2 us: +0.3-0.9 %).
 int halo3_wgrad_splits(const HaloWgradArgs& a) {
   const int groups = (a.Cout / 64) * (a.cin / 64);
-  const int n_sp = a.N * (a.H / 8) * (a.W / HW_TW);
+  const int n_sp = halo_tiles(a.N, a.H, a.W, kWgradTH).n_sp;
   const double slab = 4.0 * a.Cout * 9.0 * a.cin;
   int best = 1;
   double best_t = 1e30;
@@ -1749,25 +1254,12 @@ int halo3_wgrad_splits(const HaloWgradArgs& a) {
 }
 
 int launch_halo3_wgrad(const HaloWgradArgs& a, int G_per, hipStream_t st) {
-  constexpr int TH = 8;
-  const int tiles_w = a.W / HW_TW, tiles_h = a.H / TH;
-  const int n_sp = a.N * tiles_h * tiles_w;
+  constexpr int TH = kWgradTH;
+  const HaloTiles t = halo_tiles(a.N, a.H, a.W, TH);
   const int groups = (a.Cout / 64) * (a.cin / 64);
   const size_t lds = 2 * ((size_t)TH * HW_TW + (size_t)(TH + 2) * (HW_TW + 2)) * 128;
-  static const bool w4 = getenv("UNETSEG_HALO_WG_W4") != nullptr;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&halo3_wgrad_kernel<TH, 8>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&halo3_wgrad_kernel<TH, 4>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
-  if (w4)
-    hipLaunchKernelGGL((halo3_wgrad_kernel<TH, 4>), dim3(groups * G_per), dim3(256), lds, st, a, tiles_w, tiles_h,
-                       n_sp, G_per);
-  else
-    hipLaunchKernelGGL((halo3_wgrad_kernel<TH, 8>), dim3(groups * G_per), dim3(512), lds, st, a, tiles_w, tiles_h,
-                       n_sp, G_per);
+  allow_lds<&halo3_wgrad_kernel<TH, 8>>(lds);
+  hipLaunchKernelGGL((halo3_wgrad_kernel<TH, 8>), dim3(groups * G_per), dim3(512), lds, st, a, t.tiles_w, t.tiles_h,
+                     t.n_sp, G_per);
   return 0;
 }
