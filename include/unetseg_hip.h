@@ -414,6 +414,26 @@ int unetseg_tta_views(const float* x, int B, int C, int H, int W, int views, flo
  * 1 <= C <= 32; every output is finite. */
 int unetseg_tta_merge(const float* logits, int B, int C, int H, int W, int views, float* out, void* stream);
 
+/* ---- connected components of a class map (no reference counterpart; unetseg_hip/ccl.py) -----------
+ * cls int32 [N][H][W]: values are compared for equality only, class 0 is background.  Two pixels of one
+ * image are joined iff they have equal class and are edge neighbours, or diagonal neighbours where that
+ * class is 8-connected: the non-zero classes have `connectivity` (4 or 8), class 0 the dual (4 for 8,
+ * 8 for 4).  A component's name is its root: the smallest raster index y * W + x among its pixels.
+ * H * W <= 2^31 - 1 per image; offsets across the batch are 64-bit.  Every call checks its arguments
+ * before any launch; none waits on the host. */
+/* the tile of the label pass (host only): its seams lie at the multiples of *tw and *th */
+int unetseg_ccl_tile(int* tw, int* th);
+/* root int32 [N][H][W] = the root of every pixel's component; also the pass's only scratch */
+int unetseg_ccl_label(const int32_t* cls, int N, int H, int W, int connectivity, int32_t* root, void* stream);
+/* stats int32 [4][N][H][W], planes area, ymax, xmin, xmax, from root as unetseg_ccl_label wrote it:
+ * meaningful at root positions; elsewhere area is 0 and the rest unspecified.  ymin is the root's row. */
+int unetseg_ccl_stats(const int32_t* root, int N, int H, int W, int32_t* stats, void* stream);
+/* out int32 [N][H][W] (not cls) = cls with every component of area < threshold relabelled; root and
+ * stats as the two calls above wrote them for cls.  step 1: components of a non-zero class become 0.
+ * step 2: class-0 components that touch no image border take the class of the pixel above their root. */
+int unetseg_ccl_filter(const int32_t* cls, const int32_t* root, const int32_t* stats, int N, int H, int W, int step,
+                       int threshold, int32_t* out, void* stream);
+
 /* ---- device augmentation of the loader (utils/hf_dataloader.py:67-105, 111-180, 183-213) -------
  * Replaces HFUnetDataset.get_random_data + preprocess + hf_unet_dataset_collate for one batch:
  * PIL BICUBIC image / NEAREST mask resize (bit-exact), flip, paste on the grey / zero canvas,

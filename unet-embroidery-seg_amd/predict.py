@@ -19,11 +19,20 @@ class probabilities blended back into one map (csrc/tiles.hip, utils/tiling.py).
 ``--tta MODE`` (no reference counterpart) wraps the loaded model in ``unetseg_hip.tta.TTA``: every
 forward runs on the flips / quarter turns of its input and returns the log of the mean class
 probabilities (csrc/tta.hip), which both paths take as logits.  The default, ``none``, wraps nothing.
+
+``--min-area N`` / ``--max-hole N`` (no reference counterpart) clean the label map of either path on
+the device, before the download: every connected component of a non-zero class smaller than N pixels
+becomes background, then every background component smaller than N pixels that touches no image border
+is filled with the class above it (csrc/ccl.hip, unetseg_hip/ccl.py).  ``--connectivity`` (8 or 4) is
+that of the non-zero classes; the background takes the dual.  ``--components`` also writes
+``<name>_components.json`` beside the mask: class, area and box of every component of the cleaned
+map.  The defaults (0, 0, 8, off) launch nothing and leave the output as it was.
 """
 from __future__ import annotations
 
 import argparse
 import colorsys
+import json
 import os
 import sys
 import time
@@ -38,6 +47,7 @@ import torch  # noqa: E402
 from PIL import Image  # noqa: E402
 
 from model.model_factory import SUPPORTED_MODELS, build_model  # noqa: E402
+from unetseg_hip import ccl  # noqa: E402
 from unetseg_hip.lib import lib  # noqa: E402
 from unetseg_hip.tta import MODES as TTA_MODES, TTA  # noqa: E402
 from utils import tiling  # noqa: E402
@@ -86,8 +96,18 @@ def letterbox(image, device):
     return x, nw, nh
 
 
-def predict_labels(model, image, device):
-    """predict.py:72-93: the argmax label map int32 [H][W] at the image's original size"""
+def finish_labels(labels, min_area=0, max_hole=0, connectivity=8, components=False):
+    """the device label map cleaned (unetseg_hip.ccl.clean) and downloaded; with ``components`` also the
+    cleaned map's component table int32 [K][7], (image, class, area, ymin, xmin, ymax, xmax)"""
+    labels = ccl.clean(labels, min_area, max_hole, connectivity)
+    if components:
+        return labels.cpu().numpy(), ccl.components(labels, connectivity).cpu().numpy()
+    return labels.cpu().numpy()
+
+
+def predict_labels(model, image, device, min_area=0, max_hole=0, connectivity=8, components=False):
+    """predict.py:72-93: the argmax label map int32 [H][W] at the image's original size, cleaned as
+    ``finish_labels`` says (and followed by the component table when ``components`` is set)"""
     x, nw, nh = letterbox(image, device)
     with torch.no_grad():
         pr = model(x)[0].float().contiguous()
@@ -96,15 +116,17 @@ def predict_labels(model, image, device):
     labels = torch.empty(oh, ow, dtype=torch.int32, device=device)
     lib.softmax_resize_argmax(pr.data_ptr(), C, H, W, (INPUT_SHAPE[0] - nh) // 2, (INPUT_SHAPE[1] - nw) // 2, nh, nw,
                               oh, ow, labels.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
-    return labels.cpu().numpy()
+    return finish_labels(labels, min_area, max_hole, connectivity, components)
 
 
-def predict_labels_tiled(model, image, device, tile=512, overlap=64, tile_batch=8, bf16=False, return_probs=False):
+def predict_labels_tiled(model, image, device, tile=512, overlap=64, tile_batch=8, bf16=False, return_probs=False,
+                         min_area=0, max_hole=0, connectivity=8, components=False):
     """the argmax label map int32 [H][W] of the image at its native resolution: overlapping tiles
     (utils/tiling.py) gathered on the device, ``model`` (any callable [B,3,t,t] fp32 -> [B,C,t,t]
     logits, C >= 2) run over ranges of ``tile_batch`` tiles, the window-weighted softmax of every tile
-    accumulated in ascending tile order and normalised.  With ``return_probs`` also the blended fp32
-    probabilities [C][H][W]."""
+    accumulated in ascending tile order and normalised, the label map cleaned as ``finish_labels`` says.
+    With ``return_probs`` also the blended fp32 probabilities [C][H][W] (of the map before cleaning);
+    with ``components`` the component table comes last."""
     tiling.check(tile, overlap)
     rgb = np.array(image, np.uint8)  # a writable C-contiguous copy (a PIL image's buffer is read-only)
     if rgb.ndim != 3 or rgb.shape[2] != 3:
@@ -134,9 +156,10 @@ def predict_labels_tiled(model, image, device, tile=512, overlap=64, tile_batch=
     probs = torch.empty_like(acc) if return_probs else None
     lib.tile_finish(acc.data_ptr(), acc.shape[0], H, W, tile, overlap, probs.data_ptr() if return_probs else None,
                     labels.data_ptr(), st)
+    done = finish_labels(labels, min_area, max_hole, connectivity, components)
     if return_probs:
-        return labels.cpu().numpy(), probs.cpu().numpy()
-    return labels.cpu().numpy()
+        return (done[0], probs.cpu().numpy(), done[1]) if components else (done, probs.cpu().numpy())
+    return done
 
 
 def check_tiling(tile, overlap, tile_batch=8):
@@ -152,6 +175,22 @@ def check_tiling(tile, overlap, tile_batch=8):
         raise ValueError(f"--tile-batch must be positive, got {tile_batch}")
 
 
+def check_clean(min_area, max_hole, connectivity):
+    """the command line's cleanup options: thresholds >= 0 (0 = off), connectivity 4 or 8"""
+    if min_area < 0:
+        raise ValueError(f"--min-area must not be negative, got {min_area}")
+    if max_hole < 0:
+        raise ValueError(f"--max-hole must not be negative, got {max_hole}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"--connectivity must be 4 or 8, got {connectivity}")
+
+
+def components_json(table):
+    """the component table as the list ``--components`` writes: class, area, bbox [x0, y0, x1, y1], in table order"""
+    return [{"class": int(c), "area": int(a), "bbox": [int(x0), int(y0), int(x1), int(y1)]}
+            for _, c, a, y0, x0, y1, x1 in table]
+
+
 def blend(old, seg, alpha=0.7):
     """cv2.addWeighted(old, 1 - alpha, seg, alpha, 0) for uint8 (float32 arithmetic, round half even)"""
     f = np.float32
@@ -160,8 +199,9 @@ def blend(old, seg, alpha=0.7):
 
 
 def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, device=None, tile=0, overlap=64,
-                 tile_batch=8, bf16=False):
-    """predict.py:41-109; tile > 0 takes the label map from predict_labels_tiled"""
+                 tile_batch=8, bf16=False, min_area=0, max_hole=0, connectivity=8, components=False):
+    """predict.py:41-109; tile > 0 takes the label map from predict_labels_tiled; ``components`` writes
+    the cleaned map's component list to ``<name>_components.json`` beside the mask"""
     try:
         image = Image.open(file_path)
     except (FileNotFoundError, IOError) as e:
@@ -170,16 +210,26 @@ def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, devic
     device = device or torch.device("cuda")
     image = cvtColor(image)
     old_img = image.copy()
+    # only the cleanup options that are set: without any, the two calls are what they were before cleanup existed
+    post = {k: v for k, v in (("min_area", min_area), ("max_hole", max_hole), ("components", components)) if v}
+    if post:
+        post["connectivity"] = connectivity
     if tile:
-        pr = predict_labels_tiled(model, image, device, tile=tile, overlap=overlap, tile_batch=tile_batch, bf16=bf16)
+        pr = predict_labels_tiled(model, image, device, tile=tile, overlap=overlap, tile_batch=tile_batch, bf16=bf16,
+                                  **post)
     else:
-        pr = predict_labels(model, image, device)
+        pr = predict_labels(model, image, device, **post)
+    if components:
+        pr, table = pr
     oh, ow = pr.shape
     seg_img = np.reshape(np.array(colors_for(num_classes), np.uint8)[np.reshape(pr, [-1])], [oh, ow, -1])
     out = Image.fromarray(blend(np.array(old_img), seg_img)) if mix_type else Image.fromarray(np.uint8(seg_img))
     save_path = os.path.join(exp_folder, os.path.splitext(os.path.basename(file_path))[0] + "_mask.png")
     out.save(save_path)
     print(f"Mask saved at: {save_path}")
+    if components:
+        with open(save_path[:-len("_mask.png")] + "_components.json", "w") as f:
+            json.dump(components_json(table), f)
     return save_path
 
 
@@ -198,6 +248,7 @@ def create_val_exp_folder(root="run"):
 def predict(args):
     """predict.py:112-145"""
     check_tiling(args.tile, args.overlap, args.tile_batch)
+    check_clean(args.min_area, args.max_hole, args.connectivity)
     exp_folder = create_val_exp_folder(args.out_dir)
     num_classes = args.num_classes + 1
     assert os.path.exists(args.weights), f"weights {args.weights} not found."
@@ -215,7 +266,8 @@ def predict(args):
         raise ValueError(f"Unsupported input path: {args.data_path}")
     t0 = time_synchronized()
     saved = [detect_image(f, model, num_classes, exp_folder, mix_type=args.mix_type, device=device, tile=args.tile,
-                          overlap=args.overlap, tile_batch=args.tile_batch, bf16=args.bf16)
+                          overlap=args.overlap, tile_batch=args.tile_batch, bf16=args.bf16, min_area=args.min_area,
+                          max_hole=args.max_hole, connectivity=args.connectivity, components=args.components)
              for f in files if f.endswith((".jpg", ".png", ".jpeg"))]
     print(f"inference time for: {time_synchronized() - t0}")
     return saved
@@ -238,6 +290,16 @@ def parse_args(argv=None):
     p.add_argument("--tta", default="none", choices=list(TTA_MODES),
                    help="test-time augmentation: average the class probabilities over the mirror (hflip), the "
                         "mirror and the half turn (flips) or all eight flips and quarter turns (d4) of each input")
+    p.add_argument("--min-area", default=0, type=int,
+                   help="components of a non-zero class smaller than this many pixels become background (0: off)")
+    p.add_argument("--max-hole", default=0, type=int,
+                   help="background components smaller than this many pixels that touch no image border are "
+                        "filled with the class above them, after --min-area (0: off)")
+    p.add_argument("--connectivity", default=8, type=int, choices=[4, 8],
+                   help="of the non-zero classes; the background takes the other")
+    p.add_argument("--components", action="store_true",
+                   help="also write <name>_components.json: class, area and bbox [x0, y0, x1, y1] of every "
+                        "component of the cleaned label map")
     return p.parse_args(argv)
 
 

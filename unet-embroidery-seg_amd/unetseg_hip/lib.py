@@ -134,6 +134,10 @@ SIGNATURES = {
     "unetseg_tile_finish": (I, [P, I, I, I, I, I, P, P, P]),
     "unetseg_tta_views": (I, [P, I, I, I, I, I, P, P]),
     "unetseg_tta_merge": (I, [P, I, I, I, I, I, P, P]),
+    "unetseg_ccl_tile": (I, [P, P]),
+    "unetseg_ccl_label": (I, [P, I, I, I, I, P, P]),
+    "unetseg_ccl_stats": (I, [P, I, I, I, P, P]),
+    "unetseg_ccl_filter": (I, [P, P, P, I, I, I, I, I, P, P]),
 }
 
 #: functions returning a value rather than a status (no RuntimeError on non-zero)
