@@ -259,14 +259,20 @@ int unetseg_upsample2x_bwd(int dtype, const void* dy, int ldy, int n, int h, int
  * upsample its sole consumer; reference model/unet_resnet.py:25-33 unetUp conv2 -> ReLU -> next
  * block's UpsamplingBilinear2d): dx = (A > 0) ? adjoint(dy) : 0 (no accumulate); part fp32
  * [rows][2][c], slot 0 = per-block column sums of dx (the conv's bias-gradient partials,
- * unetseg_colsum_rows); rows = unetseg_upsample2x_bwd_tiles(...) */
+ * unetseg_colsum_rows); rows = unetseg_upsample2x_bwd_tiles(...).  The channel vectors c / V must divide 256
+ * (the block's column-sum layout); any other count is an argument error. */
 int unetseg_upsample2x_bwd_tiles(int dtype, int n, int h, int w, int c);
 int unetseg_upsample2x_bwd_relu(int dtype, const void* dy, int ldy, int n, int h, int w, int c, int align_corners,
                                 const void* a, int lda, void* dx, int ldx, float* part, int rows, void* stream);
 int unetseg_add(int dtype, const void* x, int ldx, void* out, int ldo, long M, int c, void* stream);
 /* general bilinear resize to (oh, ow) with ATen's source-index rule (F.interpolate(size=...):
  * model/unet_attention.py:31-33,52-53, model/unet_dualdense.py:57-58; align_corners=True for the
- * multiclass losses' logit resize, model/unet_training.py:14-15); backward is a deterministic gather */
+ * multiclass losses' logit resize, model/unet_training.py:14-15); backward is a deterministic gather.
+ * Per axis, in fp32: align_corners: src = dst * ((in-1)/(out-1)) (scale 0 when out == 1); otherwise
+ * src = max(0, fma(dst + 0.5, in/out, -0.5)) -- one fused multiply-add, rounded once: this library's rule.
+ * ATen builds that contract the expression (its GPU kernels, its AVX2 and later CPU kernels) evaluate the same;
+ * one that rounds the product first differs in l1 by at most 2^-24 * src.
+ * i0 = (int)src (at most in-1), i1 = i0 + (i0 < in-1), l1 = src - i0, l0 = 1 - l1. */
 int unetseg_resize_bilinear_fwd(int dtype, const void* x, int ldx, int n, int h, int w, int c, int oh, int ow,
                                 int align_corners, void* y, int ldy, void* stream);
 int unetseg_resize_bilinear_bwd(int dtype, const void* dy, int ldy, int n, int h, int w, int c, int oh, int ow,

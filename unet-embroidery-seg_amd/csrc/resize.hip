@@ -5,9 +5,11 @@
 //                                                           model/unet_dualdense.py:57-58
 //   F.interpolate(..., align_corners=True) of CE/Focal/Dice  model/unet_training.py:14-15,36-37,71-72
 //   F.pad (pad-then-cat)                                    model/unet_plain.py:42-45
-// Source coordinates follow ATen's upsample_bilinear2d exactly (area_pixel_compute_source_index):
+// Source coordinates follow ATen's upsample_bilinear2d (area_pixel_compute_source_index):
 //   align_corners: src = dst * (in-1)/(out-1)  (0 when out == 1)
-//   otherwise:     src = max(0, (dst + 0.5) * in/out - 0.5)
+//   otherwise:     src = max(0, fma(dst + 0.5, in/out, -0.5))   (one rounding: this library's rule, and ATen's
+//                  where its build contracts the expression -- GPU, AVX2 and later; an unfused build differs in
+//                  l1 by at most 2^-24 * src)
 //   i0 = (int)src, i1 = i0 + (i0 < in-1), l1 = src - i0, l0 = 1 - l1   (fp32)
 // The backward is a deterministic GATHER: every input pixel sums, in a fixed order, the output
 // pixels whose source row/column pair names it, with the forward's own weights recomputed.
@@ -20,7 +22,9 @@ struct Axis {
   bool align;
   float scale;
   __device__ __forceinline__ void src(int d, int& i0, int& i1, float& l1) const {
-    float s = align ? (float)d * scale : fmaxf(((float)d + 0.5f) * scale - 0.5f, 0.f);
+    // explicit fmaf: the rounding the compiler's contraction chose, no longer its choice (forward and backward
+    // must name the same taps)
+    float s = align ? (float)d * scale : fmaxf(fmaf((float)d + 0.5f, scale, -0.5f), 0.f);
     i0 = (int)s;
     if (i0 > in - 1) i0 = in - 1;
     i1 = i0 + (i0 < in - 1 ? 1 : 0);

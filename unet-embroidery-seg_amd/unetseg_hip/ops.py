@@ -1097,8 +1097,9 @@ def _is_relu_of(x, X):
 
 def _upsample_may_fuse(ctx, x, X):
     # beyond the shared test: upsample2x_bwd_relu has the plain ReLU only and masks with X (_is_relu_of);
-    # FUSE_UP is this fusion's own switch
-    return FUSE_UP and _sole_relu_consumer(ctx, x) and _is_relu_of(x, X)
+    # FUSE_UP is this fusion's own switch.  The kernel's column-sum layout needs the 8-channel vectors (bf16:
+    # _sole_relu_consumer) to divide 256; any other channel count takes upsample2x_bwd and the ReLU's own backward
+    return FUSE_UP and _sole_relu_consumer(ctx, x) and _is_relu_of(x, X) and 256 % (X.shape[-1] // 8) == 0
 
 
 def _head_may_fuse(ctx, x, X):
