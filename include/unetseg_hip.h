@@ -99,10 +99,10 @@ int unetseg_conv2d_fwd_affine(int dtype, const void* x1, int c1, int ldc1, const
                               const float* escale, const float* bias, int relu, void* y, int ldy, void* stream);
 /* Kernel-configuration queries (host only, nothing is launched; replace no reference operator:
  * they let the parity tests assert that they exercise every kernel configuration the benchmark
- * selects).  Codes: 0 = halo3 (64-channel 3x3 kernel), 1..14 = TN tile configuration
- * (conv_fast.hip tn_config: 1 256x64, 2 256x128, 3 128x128, 4 128x128 one K step, 5 64x128,
- * 6 128x64, 7 256x128 LDS-DMA ring, 8 128x128 ring, 9 64x128 ring, 10 128x128 5-stage ring,
- * 11-14 other rings), 17 / 18 = the parity classes of a stride-2 data gradient merged into one launch
+ * selects).  Codes: 0 = halo3 (64-channel 3x3 kernel), 2..13 = TN tile configuration
+ * (conv_fast.hip tn_config: 2 256x128, 3 128x128, 4 128x128 one K step, 5 64x128,
+ * 6 128x64, 7 256x128 LDS-DMA ring, 9 64x128 ring, 10 128x128 5-stage ring, 13 128x64 ring;
+ * 1, 8, 11, 12 and 14 are retired and not reused), 17 / 18 = the parity classes of a stride-2 data gradient merged into one launch
  * on 128x128 / 64x128 tiles, 19 / 20 = short-K (2-4 steps) 128x128 / 128x64 tiles on one LDS stage,
  * 21 / 22 / 23 = halo-A ring 256x128 / 256x64 / 128x128, 24 / 25 = the first two persistent (several tiles per
  * block), 100 = generic igemm kernel (fp32 / unaligned channels).  *taps_out = the

@@ -67,6 +67,8 @@ CASES = {
     "fwd_ring128x64_t9": ("fwd_relu", (1, 256, 256, 64, 128, 64, 3, 1), ["fwd:ring128x64_t9"]),  # up_concat1.conv1
     "fwd_ring64x128_t9": ("fwd_stats", (1, 64, 64, 256, 0, 256, 3, 2), ["fwd:ring64x128_t9"]),
     "fwd_ring64x128_t1": ("fwd_stats", (1, 16, 16, 2048, 0, 512, 1, 1), ["fwd:ring64x128_t1"]),
+    # the generic ring (25 taps, not known at compile time: no _t suffix): 5x5 stride 1, 50 K steps, 2 tiles
+    "fwd_ring64x128_5x5": ("fwd_stats", (1, 16, 16, 128, 0, 128, 5, 1), ["fwd:ring64x128"]),
     "fwd_tn128x128_1st": ("fwd_all", (1, 64, 64, 128, 0, 512, 1, 1), ["fwd:tn128x128_1st"]),
     "fwd_tn128x128_1step": ("fwd_stats", (1, 128, 128, 64, 0, 256, 1, 1), ["fwd:tn128x128_1step"]),
     "fwd_tn128x64": ("fwd_stats", (1, 32, 32, 512, 0, 64, 1, 1), ["fwd:tn128x64"]),
@@ -90,6 +92,7 @@ CASES = {
     "dgrad_ring128x64_t9": ("dgrad", (1, 256, 256, 64, 0, 128, 3, 1), ["dgrad:ring128x64_t9"]),  # attention down1
     "dgrad_ring64x128_t9": ("dgrad", (1, 32, 32, 256, 0, 256, 3, 1), ["dgrad:ring64x128_t9"]),
     "dgrad_ring64x128_t1": ("dgrad", (1, 16, 16, 512, 0, 2048, 1, 1), ["dgrad:ring64x128_t1"]),
+    "dgrad_ring64x128_5x5": ("dgrad", (1, 16, 16, 128, 0, 128, 5, 1), ["dgrad:ring64x128"]),
     "dgrad_tn128x128_1st": ("dgrad", (1, 64, 64, 512, 0, 128, 1, 1), ["dgrad:tn128x128_1st"]),
     "dgrad_tn128x128_1st_bench": ("dgrad", (16, 128, 128, 256, 0, 128, 1, 1), ["dgrad:tn128x128_1st"]),  # layer2 conv1
     "dgrad_tn128x128_s2": ("dgrad", (2, 64, 64, 256, 0, 512, 1, 2),

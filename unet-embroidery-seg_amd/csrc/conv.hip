@@ -1563,8 +1563,6 @@ struct StemPlan {
 
 // The stem's forward dispatch: the persistent-halo stem kernel (conv_halo.hip) when the output tiles
 // into 16 x 32 pixels, else a TN tile of the fast kernels, else the shape is unsupported.
-// UNETSEG_STEM_CFG = a register-staged or generic-ring TN configuration (1, 2, 3, 5, 6, 8, 11, 12, 13,
-// 14) for experiments, else tn_config's rule.
 // The halo kernel always writes BN statistics, so unetseg_stem_fwd takes it only when the caller wants
 // them (has_stats); the queries (unetseg_stem_fwd_tile_m, unetseg_stem_config) assume it does, and a
 // dense output (ldy = K).
@@ -1579,9 +1577,6 @@ static StemPlan plan_stem(const void* xp, int n, int h, int w, const void* wk, i
   IgemmArgs a = stem_args(xp, n, h, w, wk, K);
   a.y = y; a.ldy = ldy; a.accumulate = 0; a.bias = nullptr; a.relu = 0; a.stats = stats;
   if (!fast_tn_args(a, p.f)) return p;
-  static const int forced = getenv("UNETSEG_STEM_CFG") ? atoi(getenv("UNETSEG_STEM_CFG")) : 0;
-  if (forced == 1 || forced == 2 || forced == 3 || forced == 5 || forced == 6 || forced == 8 || (forced >= 11 && forced <= 14))
-    p.f.force_cfg = forced;
   p.kind = kStemFast;
   return p;
 }

@@ -1,4 +1,5 @@
-// Argument blocks of the fast bf16 conv kernels (conv_fast.hip), dispatched from conv.hip.
+// Argument blocks of the fast bf16 conv kernels (conv_fast.hip, conv_tn_persist.hip, conv_wgrad_fast.hip,
+// conv_wgrad_ring.hip, conv_halo.hip, conv_first.hip), dispatched from conv.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -51,7 +52,6 @@ struct FastTNArgs {
   int ld_aux2;
   const float* pmean2;
   const float* pinv2;
-  int t2d;  // rows of a 2D spatial tile (BM = t2d x 32 pixels), 0 = row-major GEMM rows (set by the launcher)
   // input prologue: x1 is the producer's BN input z, the conv reads relu(z * in_sc[c] + in_sh[c])
   // (its BN-ReLU output, never materialised); register-staged configurations only, x2 == NULL
   const float* in_sc;
@@ -62,12 +62,6 @@ struct FastTNArgs {
   const float* head_b;
   float* head_y;
   int head_k;
-  // issue-order options of the LDS-DMA ring (set by the launcher; UNETSEG_TN_SCHED): bit 0 = the
-  // waves of the second SIMD pair issue their K step's DMAs after the first K half's MFMAs
-  int sched;
-  // a TN configuration chosen by the caller instead of tn_config's rule (0: the rule) -- the stem's
-  // experiments (UNETSEG_STEM_CFG)
-  int force_cfg;
   // halo forward with bias + ReLU: also store the output's ReLU mask as bits, [M][Ng/8] (bit e of byte
   // b = channel 8b + e > 0); post 4 = post 1 with the mask read from such bits (mbits, halo path only)
   unsigned char* mbits_out;
@@ -104,18 +98,28 @@ struct HaloWgradArgs {
   float* ws;
 };
 
-// kernel-configuration codes reported by the unetseg_conv2d_*_config queries (include/unetseg_hip.h)
-// 1..14: TN tile configurations of tn_config (conv_fast.hip); 17 / 18: stride-2 dgrad parity classes
-// merged into one launch on 128x128 / 64x128 register-staged tiles (launch_tn_multi); 19 / 20: short K
-// (2-4 steps) on one LDS stage, 128x128 / 128x64; 21-23: halo-A rings 256x128 / 256x64 / 128x128; 24 / 25:
-// the 256x128 / 256x64 halo-A rings persistent (tn_halo_persist_kernel, several tiles per block)
-enum { kCfgHalo = 0, kCfgMulti128 = 17, kCfgMulti64 = 18, kCfgStemHalo = 30, kCfgFirst3x3 = 31, kCfgGeneric = 100 };
+// kernel-configuration codes reported by the unetseg_conv2d_*_config queries (include/unetseg_hip.h;
+// the values are part of the C ABI, of tests/golden/conv_dispatch.json and of lib.py's CFG_NAMES, so a
+// retired code's value -- 1, 8, 11, 12, 14 -- is not reused).  2-6: register-staged TN tiles, 7-13: the
+// same tiles on the LDS-DMA gather ring, 19 / 20: short K on one LDS stage, 21-23: halo-A rings -- each
+// described by one record in conv_fast.hip's kTnTable; 17 / 18: stride-2 dgrad parity classes merged
+// into one launch on 128x128 / 64x128 register-staged tiles (launch_tn_multi); 24 / 25: the 256x128 /
+// 256x64 halo-A rings persistent (conv_tn_persist.hip, several tiles per block)
+enum { kCfgHalo = 0, kCfgTn256x128 = 2, kCfgTn128x128 = 3, kCfgTn128x128Step1 = 4, kCfgTn64x128 = 5, kCfgTn128x64 = 6,
+       kCfgRing256x128 = 7, kCfgRing64x128 = 9, kCfgRing128x128S5 = 10, kCfgRing128x64 = 13,
+       kCfgMulti128 = 17, kCfgMulti64 = 18, kCfgShort128x128 = 19, kCfgShort128x64 = 20,
+       kCfgHaloA256x128 = 21, kCfgHaloA256x64 = 22, kCfgHaloA128x128 = 23, kCfgPersist256x128 = 24, kCfgPersist256x64 = 25,
+       kCfgStemHalo = 30, kCfgFirst3x3 = 31, kCfgGeneric = 100 };
 enum { kWgHalo = 0, kWgFastRow64x256 = 1, kWgFastRow128 = 2, kWgFast64x256 = 3, kWgFast128 = 4, kWgGeneric = 5,
        kWgRing64x256 = 6, kWgRing128 = 7 };
 
 bool tn_fast_ok(const FastTNArgs& a);
-int tn_fast_config(const FastTNArgs& a, int* taps_out);  // kCfgHalo or a TN configuration 1..14
+int tn_fast_config(const FastTNArgs& a, int* taps_out);  // kCfgHalo or a TN configuration of kTnTable / 24 / 25
 int launch_tn_fast(const FastTNArgs& a, hipStream_t st);
+// the persistent halo-A ring (conv_tn_persist.hip) on bn-wide (128 / 64) column tiles: tiles per block, or 0
+// when the call keeps the one-tile-per-block kernel; the launch (-1 without launching when it is 0)
+int tn_persist_tiles(const FastTNArgs& a, int bn);
+int launch_tn_persist(const FastTNArgs& a, int bn, int ha, hipStream_t st);  // ha: the tile's halo pieces (TnCfg::HA)
 // 2-4 independent GEMMs (stride-2 dgrad parity classes) in one launch: the shared row tile (64 /
 // 128), or -1 if they cannot be merged; launch_tn_multi returns -1 without launching in that case
 int tn_multi_tile_m(const FastTNArgs* fs, int n);

@@ -1,5 +1,5 @@
 // Weight gradient on an LDS-DMA ring (bf16, gfx950): the 1x1 / strided / small-grid shapes of the
-// wgrad_fast family (conv_fast.hip) whose K steps are whole 32-pixel runs.  Its own translation unit
+// wgrad_fast family (conv_wgrad_fast.hip) whose K steps are whole 32-pixel runs.  Its own translation unit
 // because it is built with MFMA accumulators in VGPRs (-mllvm -amdgpu-mfma-vgpr-form, Makefile):
 // with AGPR accumulators the register allocator rotates all 64 of them through v_accvgpr_mov every
 // K step (as much issue time as the step's 16 MFMAs); the other conv kernels are unaffected by

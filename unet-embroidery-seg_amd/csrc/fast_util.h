@@ -1,4 +1,5 @@
-// Device helpers shared by the fast bf16 conv kernels (conv_fast.hip, conv_halo.hip).
+// Device helpers shared by the fast bf16 conv kernels (conv_fast.hip, conv_tn_persist.hip,
+// conv_wgrad_fast.hip, conv_wgrad_ring.hip, conv_halo.hip, conv_first.hip).
 #pragma once
 #include "common.h"
 
@@ -137,6 +138,15 @@ __device__ __forceinline__ void row16_sum_n(float (&v)[N]) {
   ROW16_STEP(0x122)
   ROW16_STEP(0x121)
 #undef ROW16_STEP
+}
+
+// halo-A rings (conv_fast.hip, conv_tn_persist.hip): 16-B chunks of one (padded) halo stage of a BM-row
+// tile ((BM / 32 + 2) x 34 pixels) -- every wave issues the same number of halo DMA instructions, so the
+// stage is rounded up to whole instructions of the block
+template <int BM, int NWM, int NWN>
+constexpr int kHaloChunks() {
+  constexpr int NT = 64 * NWM * NWN;  // rounded to instruction pairs (issued two at a time)
+  return ((BM / 32 + 2) * 34 * 8 + 2 * NT - 1) / (2 * NT) * (2 * NT);
 }
 
 }  // namespace

@@ -39,7 +39,7 @@ _QMEMO = {}
 
 #: dispatch switches the library reads on every call (not once per process): tests flip them
 #: in-process, so each is part of the query memo's key (conv.hip / conv_fast.hip / elem.hip / pool.hip / upsample.hip getenv)
-_CALL_SWITCHES = ("UNETSEG_TN_NO_HALO_RING", "UNETSEG_TN_CFG", "UNETSEG_TN_CFG_NO23", "UNETSEG_NO_FAST",
+_CALL_SWITCHES = ("UNETSEG_TN_NO_HALO_RING", "UNETSEG_TN_CFG", "UNETSEG_NO_FAST",
                   "UNETSEG_RED_TARGET", "UNETSEG_MAXPOOL_GENERIC")
 _ENV = os.environ
 
