@@ -39,7 +39,30 @@ int unetseg_device_arch(char* buf, int n);
 /* ---- convolution (nn.Conv2d: model/resnet_backbone.py:19,33,126,167; model/unet_resnet.py:17,19,
  *      72,74,78; model/unet_plain.py:9,12,69; model/unet_attention.py:16,20,24,76;
  *      model/unet_multitask.py:17,18,62,64,69) and the concat feeding it
- *      (torch.cat: model/unet_resnet.py:34, model/unet_plain.py:46, model/unet_attention.py:54) --- */
+ *      (torch.cat: model/unet_resnet.py:34, model/unet_plain.py:46, model/unet_attention.py:54) ---
+ *
+ * The channel-slice contract (tests/test_gpu_conv_strided.py holds every kernel configuration to it).
+ * Every activation operand of the entry points of this section is a channel slice [c0, c0 + C) of a buffer
+ * whose pixels are `ld` elements apart: the call passes the address of channel c0 of the first pixel and ld.
+ *  - Strides honoured: unetseg_conv2d_fwd / _fwd_affine ldc1, ldc2 (the two sources may differ) and ldy;
+ *    _fwd_bnrelu_in, _fwd_head, _fwd_mask ldc1 and ldy (the mask bits stay dense, [M][8]); unetseg_conv2d_dgrad
+ *    ldy (dy) and ldx (dx, written or accumulated); _dgrad_post ldy, ldx and ld_aux, each its own (post 4: the
+ *    bits are dense and ld_aux is ignored); _dgrad_post_res ldy, ldx, ld1 (y1) and ld2 (y2), each its own (its
+ *    bits dense, [M][cin / 8]); unetseg_conv2d_wgrad / _wgrad_rows / _wgrad_bnrelu_in ldc1, ldc2 and ldy (dy);
+ *    unetseg_stem_fwd / unetseg_stem_wgrad ldy (y, dy; the packed input xp is dense).  The first-3x3 kernel is
+ *    taken only with ldc1 == 8 (the packed image); any other ldc1 runs the generic kernel.  Weights, biases,
+ *    statistics, partials, dw and the workspace are dense.
+ *  - Alignment: every ld and every c0 is a multiple of 8 elements and the buffer's base is 16-byte aligned, so
+ *    each pixel of a slice starts on a 16-byte boundary (fp32: the same element counts, 32 bytes).
+ *  - Writes: no byte outside channels [c0, c0 + C) of the n*h*w pixels of an output is written -- not the
+ *    channels beside the slice, not the pixels before or after the tensor -- and no input is written at all.
+ *  - Reads: what lies outside a slice never influences a result.  The kernels address past a slice (padding
+ *    taps, absent rows of a partial tile) only under a bounds test or through a buffer descriptor whose extent,
+ *    pixels * ld * 2 bytes from the slice's first element, makes such a read return zero; the strided call
+ *    therefore gives, bit for bit, what the packed call (ld == C, c0 == 0) of the same values gives.
+ *  - The configuration a call runs depends on its pixel strides only through the operands' byte extents: every
+ *    operand must span less than 2^31 bytes (pixels * ld * 2) for the fast bf16 kernels, and a gather ring
+ *    keeps its compile-time taps only while its 32-bit gather offsets cover them. */
 
 /* fp32 [K][C][R][S] -> wk dtype [K][R][S][Cpad] (fwd) and, if wt != NULL, wt dtype [C][R][S][K] (dgrad) */
 int unetseg_pack_conv_weight(int dtype, const float* w, int K, int C, int R, int S, int Cpad, void* wk, void* wt,
