@@ -463,6 +463,28 @@ int unetseg_ccl_stats(const int32_t* root, int N, int H, int W, int32_t* stats, 
 int unetseg_ccl_filter(const int32_t* cls, const int32_t* root, const int32_t* stats, int N, int H, int W, int step,
                        int threshold, int32_t* out, void* stream);
 
+/* ---- boundary quality of class maps (no reference counterpart; unetseg_hip/boundary.py) -------------
+ * Maps are [N][H][W] with H, W <= 16384; `ignore` = -1 means no ignored value.  Everything is integer
+ * and bitwise reproducible.  Every call checks its arguments before any launch; none waits on the host. */
+#define UNETSEG_EDT_INF (1 << 30)
+/* edge uint8 = 1 where cls int32 == c, is not `ignore`, and one of the four edge neighbours lies inside
+ * the image, is not `ignore` and has a class != c; 0 elsewhere (the image frame is no boundary) */
+int unetseg_boundary_edges(const int32_t* cls, int N, int H, int W, int c, int ignore, uint8_t* edge, void* stream);
+/* d2 int32 = the exact squared Euclidean distance to the nearest non-zero pixel of the same image of
+ * sites uint8; UNETSEG_EDT_INF everywhere in an image without one.  d2 is the only scratch. */
+int unetseg_edt_sqdist(const uint8_t* sites, int N, int H, int W, int32_t* d2, void* stream);
+/* host only: the distance transform works on column segments and row chunks of *len pixels, so its seams
+ * lie at the multiples of *len */
+int unetseg_edt_chunk(int* len);
+/* counts int64 [2 (K + 2) + 2] +=, with eP / eG = the edge maps of pred / target for class c and dP / dG
+ * their distance transforms: [0 .. K+1] the histogram of min(dG, K + 1) over the edge pixels of eP,
+ * [K+2 .. 2K+3] that of min(dP, K + 1) over the edge pixels of eG, [2K+4] and [2K+5] the size of the
+ * intersection and of the union of {pred == c, dP <= biou_d2} and {target == c, dG <= biou_d2} without the
+ * pixels whose target is `ignore`.  0 <= biou_d2 <= K <= 65536. */
+int unetseg_boundary_counts(const int32_t* pred, const int32_t* target, const uint8_t* eP, const uint8_t* eG,
+                            const int32_t* dP, const int32_t* dG, int N, int H, int W, int c, int ignore, int K,
+                            int biou_d2, int64_t* counts, void* stream);
+
 /* ---- device augmentation of the loader (utils/hf_dataloader.py:67-105, 111-180, 183-213) -------
  * Replaces HFUnetDataset.get_random_data + preprocess + hf_unet_dataset_collate for one batch:
  * PIL BICUBIC image / NEAREST mask resize (bit-exact), flip, paste on the grey / zero canvas,

@@ -1,0 +1,230 @@
+"""Boundary quality of class maps on the HIP path (csrc/boundary.hip).
+
+A class map is an int32 tensor [H,W] or [N,H,W] on the GPU.  ``edges`` marks the pixels of a class that
+touch another class inside the image, ``sqdist`` is the exact squared Euclidean distance transform of a
+site map, and ``counts`` reduces a prediction / target pair to two edge-distance histograms and the
+Boundary-IoU intersection and union.  ``metrics_from_counts`` reads boundary precision / recall / F1 at a
+pixel tolerance, Boundary IoU (Cheng et al., CVPR 2021) and the 95th-percentile Hausdorff distance from
+such counts on the host.  All of it is integer and bitwise reproducible; ``edges``, ``sqdist`` and
+``counts`` run on the current stream and never wait on the host, and ``counts`` accumulates, so a split
+costs one host read.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import torch
+
+from .lib import lib
+
+#: ``sqdist`` of an image without a site (UNETSEG_EDT_INF)
+INF = 1 << 30
+#: largest K (a squared distance) ``counts`` takes
+MAX_K = 65536
+
+KEYS = ("Boundary Precision", "Boundary Recall", "Boundary F1", "Boundary IoU", "HD95")
+
+
+def _stream(t):
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _map(t, what="cls", dtypes=(torch.int32,)):
+    """the map as a contiguous [N,H,W] view"""
+    if not torch.is_tensor(t) or t.dtype not in dtypes or not t.is_cuda or t.dim() not in (2, 3):
+        names = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise ValueError(f"{what} must be a {names} [H,W] or [N,H,W] tensor on the GPU, got "
+                         f"{t.dtype if torch.is_tensor(t) else type(t)} "
+                         f"{tuple(t.shape) if torch.is_tensor(t) else ''}")
+    t = t.contiguous()
+    return t.unsqueeze(0) if t.dim() == 2 else t
+
+
+def _ignore(ignore_index):
+    if ignore_index is None:
+        return -1
+    if int(ignore_index) == -1:
+        raise ValueError("ignore_index -1 stands for None in the kernels; use another value")
+    return int(ignore_index)
+
+
+def chunk():
+    """the distance transform works on column segments and row chunks of this many pixels, so its seams
+    lie at the multiples"""
+    n = ctypes.c_int(0)
+    lib.edt_chunk(ctypes.addressof(n))
+    return n.value
+
+
+def edges(cls, c=1, ignore_index=None):
+    """uint8, the shape of ``cls``: 1 where the pixel has class ``c`` and one of its four edge neighbours
+    lies inside the image, is not ``ignore_index`` and has another class.  The image frame is no
+    boundary, and a pixel that is ``ignore_index`` is never an edge pixel."""
+    m = _map(cls)
+    N, H, W = m.shape
+    out = torch.empty(m.shape, dtype=torch.uint8, device=m.device)
+    lib.boundary_edges(m.data_ptr(), N, H, W, int(c), _ignore(ignore_index), out.data_ptr(), _stream(m))
+    return out.view(cls.shape)
+
+
+def sqdist(sites):
+    """int32, the shape of ``sites`` (uint8 or bool, non-zero = site): the exact squared Euclidean distance
+    to the nearest site of the same image, ``INF`` everywhere in an image without one"""
+    s = _map(sites, "sites", (torch.uint8, torch.bool))
+    if s.dtype == torch.bool:
+        s = s.view(torch.uint8)
+    N, H, W = s.shape
+    d2 = torch.empty(s.shape, dtype=torch.int32, device=s.device)
+    lib.edt_sqdist(s.data_ptr(), N, H, W, d2.data_ptr(), _stream(s))
+    return d2.view(sites.shape)
+
+
+def default_biou_d(H, W, K=4096):
+    """the Boundary-IoU paper's 2 % of the image diagonal in pixels, within [1, floor(sqrt(K))]"""
+    return max(1, min(round(0.02 * math.sqrt(H * H + W * W)), math.isqrt(K)))
+
+
+def counts(pred, target, c=1, K=4096, biou_d=None, ignore_index=None, out=None):
+    """device int64 [2 (K + 2) + 2] (+)= the boundary counts of class ``c`` of the int32 maps ``pred`` and
+    ``target`` (same shape), with eP / eG their edge maps and dP / dG the distance transforms of those:
+
+    * ``[0 .. K+1]``: the histogram of ``min(dG, K + 1)`` over the edge pixels of ``pred`` (bin K + 1: further
+      than K, or the target has no edge);
+    * ``[K+2 .. 2K+3]``: the same of ``dP`` over the edge pixels of ``target``;
+    * ``[2K+4]``, ``[2K+5]``: intersection and union of {pred == c, dP <= biou_d^2} and
+      {target == c, dG <= biou_d^2}, without the pixels whose target is ``ignore_index``.
+
+    ``K`` is a squared distance; ``biou_d`` is in pixels, None = ``default_biou_d(H, W, K)``.  ``out`` is
+    added to and returned when given."""
+    p, t = _map(pred, "pred"), _map(target, "target")
+    if p.shape != t.shape or p.device != t.device:
+        raise ValueError(f"pred {tuple(p.shape)} on {p.device} and target {tuple(t.shape)} on {t.device} differ")
+    N, H, W = p.shape
+    K = int(K)
+    if not 0 <= K <= MAX_K:
+        raise ValueError(f"K must lie in 0 .. {MAX_K}, got {K}")
+    d = default_biou_d(H, W, K) if biou_d is None else int(biou_d)
+    if d < 0 or d * d > K:
+        raise ValueError(f"biou_d = {d} px needs 0 <= biou_d^2 <= K = {K}")
+    n = 2 * (K + 2) + 2
+    if out is None:
+        out = torch.zeros(n, dtype=torch.int64, device=p.device)
+    elif (not torch.is_tensor(out) or out.dtype != torch.int64 or out.device != p.device or out.dim() != 1
+          or out.numel() != n or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous int64 [{n}] tensor on {p.device}")
+    ign = _ignore(ignore_index)
+    eP, eG = edges(p, c, ignore_index), edges(t, c, ignore_index)
+    dP, dG = sqdist(eP), sqdist(eG)
+    lib.boundary_counts(p.data_ptr(), t.data_ptr(), eP.data_ptr(), eG.data_ptr(), dP.data_ptr(), dG.data_ptr(), N, H,
+                        W, int(c), ign, K, d * d, out.data_ptr(), _stream(p))
+    return out
+
+
+def labels_from_logits(outputs):
+    """int32 [B,H,W] class map of logits [B,C,H,W]: C >= 2 the argmax with a tie going to the lower class,
+    C == 1 ``logit > 0``: the rule of ``losses.binary_confusion`` (argmax with the tie to class 0, and
+    sigmoid > 0.5, which a zero logit does not pass)"""
+    if not torch.is_tensor(outputs) or outputs.dim() != 4:
+        raise ValueError("outputs must be logits [B,C,H,W]")
+    out = outputs.detach().float()
+    if out.shape[1] == 1:
+        return (out[:, 0] > 0).to(torch.int32)
+    best, lab = out[:, 0], torch.zeros(out[:, 0].shape, dtype=torch.int32, device=out.device)
+    for k in range(1, out.shape[1]):  # strictly greater: a tie keeps the lower class
+        take = out[:, k] > best
+        best = torch.where(take, out[:, k], best)
+        lab = torch.where(take, torch.full_like(lab, k), lab)
+    return lab
+
+
+def metrics_from_counts(counts, K, tolerance=2.0):
+    """host, float64: the five ``KEYS`` from a ``counts`` array (tensor, array or list) taken with this K.
+
+    Precision / recall: the share of prediction / target edge pixels whose squared distance to the other
+    side's edge is at most ``tolerance``^2; a side without edge pixels scores 1.0 when the other has none
+    either and 0.0 otherwise.  F1 = 2 P R / (P + R), 0 when P + R == 0.  Boundary IoU =
+    intersection / union, 1.0 when the union is empty.  HD95: the two histograms pooled, sqrt of the
+    smallest bin whose cumulative count reaches 95 % of all edge pixels; ``math.inf`` when that is the
+    overflow bin, 0.0 without any edge pixel."""
+    K = int(K)
+    c = [int(v) for v in (counts.tolist() if hasattr(counts, "tolist") else counts)]
+    if len(c) != 2 * (K + 2) + 2:
+        raise ValueError(f"counts has {len(c)} entries, K = {K} needs {2 * (K + 2) + 2}")
+    t2 = float(tolerance) ** 2
+    if tolerance < 0 or t2 > K:
+        raise ValueError(f"tolerance^2 = {t2} must lie in 0 .. K = {K}")
+    hp, hg = c[:K + 2], c[K + 2:2 * K + 4]
+    inter, union = c[2 * K + 4], c[2 * K + 5]
+    n_p, n_g = sum(hp), sum(hg)
+    last = min(int(math.floor(t2)), K)  # bins 0 .. last are within the tolerance
+
+    def share(h, n, n_other):
+        if n == 0:
+            return 1.0 if n_other == 0 else 0.0
+        return float(sum(h[:last + 1])) / float(n)
+
+    prec, rec = share(hp, n_p, n_g), share(hg, n_g, n_p)
+    f1 = 2.0 * prec * rec / (prec + rec) if prec + rec > 0 else 0.0
+    biou = float(inter) / float(union) if union > 0 else 1.0
+    total, hd95 = n_p + n_g, 0.0
+    if total > 0:
+        cum = 0
+        for b in range(K + 2):
+            cum += hp[b] + hg[b]
+            if 100 * cum >= 95 * total:  # integers: no rounding at the boundary
+                hd95 = math.inf if b == K + 1 else math.sqrt(b)
+                break
+    return {"Boundary Precision": prec, "Boundary Recall": rec, "Boundary F1": f1, "Boundary IoU": biou,
+            "HD95": hd95}
+
+
+class Accumulator:
+    """the boundary counts of an evaluation loop: one device array per class, added to per batch, read once.
+
+    ``options`` is the entry points' ``boundary`` dict: ``{"tolerance": px (default 2.0), "biou_d": px or
+    None / 0 (2 % of the diagonal), "K": squared distance (default 4096)}``."""
+
+    def __init__(self, options, classes=(1,), ignore_index=None):
+        unknown = set(options) - {"tolerance", "biou_d", "K"}
+        if unknown:
+            raise ValueError(f"unknown boundary options {sorted(unknown)}")
+        self.tolerance = float(options.get("tolerance", 2.0))
+        self.biou_d = options.get("biou_d") or None
+        self.K = int(options.get("K", 4096))
+        if self.tolerance < 0 or self.tolerance ** 2 > self.K:
+            raise ValueError(f"tolerance^2 = {self.tolerance ** 2} must lie in 0 .. K = {self.K}")
+        self.classes = tuple(classes)
+        self.ignore_index = ignore_index
+        self.out = None
+
+    def add(self, pred, target):
+        """pred int32 [B,H,W] (``labels_from_logits``); target [B,H,W] or [B,1,H,W] on the same device, integer,
+        or float read as ``losses.binary_confusion`` reads it: class 1 where it equals 1, ``ignore_index`` kept"""
+        tgt = target.detach()
+        if tgt.is_floating_point():
+            lab = (tgt == 1).to(torch.int32)
+            if self.ignore_index is not None:
+                lab = torch.where(tgt == self.ignore_index, torch.full_like(lab, int(self.ignore_index)), lab)
+            tgt = lab
+        if tgt.dim() == 4 and tgt.shape[1] == 1:
+            tgt = tgt[:, 0]
+        tgt = tgt.to(torch.int32)
+        if self.out is None:
+            self.out = torch.zeros(len(self.classes), 2 * (self.K + 2) + 2, dtype=torch.int64, device=pred.device)
+        for c, out in zip(self.classes, self.out):
+            counts(pred, tgt, c, self.K, self.biou_d, self.ignore_index, out)
+
+    def metrics(self):
+        """the five keys after one host read; with several classes the mean over those with a target edge
+        pixel in the split, 0.0 without one"""
+        n = 2 * (self.K + 2) + 2
+        rows = self.out.tolist() if self.out is not None else [[0] * n for _ in self.classes]
+        if len(self.classes) > 1:
+            rows = [c for c in rows if sum(c[self.K + 2:2 * self.K + 4]) > 0]
+        per = [metrics_from_counts(c, self.K, self.tolerance) for c in rows]
+        if not per:
+            return dict.fromkeys(KEYS, 0.0)
+        if len(per) == 1:
+            return per[0]
+        return {k: sum(m[k] for m in per) / len(per) for k in KEYS}

@@ -138,6 +138,10 @@ SIGNATURES = {
     "unetseg_ccl_label": (I, [P, I, I, I, I, P, P]),
     "unetseg_ccl_stats": (I, [P, I, I, I, P, P]),
     "unetseg_ccl_filter": (I, [P, P, P, I, I, I, I, I, P, P]),
+    "unetseg_boundary_edges": (I, [P, I, I, I, I, I, P, P]),
+    "unetseg_edt_sqdist": (I, [P, I, I, I, P, P]),
+    "unetseg_edt_chunk": (I, [P]),
+    "unetseg_boundary_counts": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, P, P]),
 }
 
 #: functions returning a value rather than a status (no RuntimeError on non-zero)

@@ -16,6 +16,7 @@ import torch
 from torch.amp import autocast
 
 from unetseg_hip import losses
+from unetseg_hip.boundary import Accumulator as BoundaryAccumulator, labels_from_logits
 from utils.utils import get_lr
 
 
@@ -153,9 +154,18 @@ def train_one_epoch_binary(model, optimizer, train_loader, device, loss_name: st
     return float(epoch_loss.item()) / max(seen_batches, 1)
 
 
-def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignore_index=None, max_batches=None):
-    """train_and_eval.py:266-305: eval-mode fp32 forward, global tp/fp/fn/tn, metrics with eps 1e-7."""
+def _boundary_acc(boundary, classes=(1,), ignore_index=None):
+    """the boundary-count accumulator of an evaluation loop, or None without the `boundary` options"""
+    return None if boundary is None else BoundaryAccumulator(boundary, classes, ignore_index)
+
+
+def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignore_index=None, max_batches=None,
+                    boundary=None):
+    """train_and_eval.py:266-305: eval-mode fp32 forward, global tp/fp/fn/tn, metrics with eps 1e-7.
+    boundary: None, or {"tolerance": px, "biou_d": px or None} to add the boundary metrics of class 1
+    (unetseg_hip/boundary.py), counted on the device and read with the confusion counts."""
     model_eval = model.eval().to(device)
+    bacc = _boundary_acc(boundary, (1,), ignore_index)
     total_loss = torch.zeros((), dtype=torch.float64, device=device)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     seen_batches = 0
@@ -166,12 +176,16 @@ def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignor
             loss = binary_segmentation_loss(outputs, pngs, loss_name, pos_weight, ignore_index)
             total_loss += loss
             losses.binary_confusion(outputs, pngs, conf, ignore_index)
+            if bacc is not None:
+                bacc.add(labels_from_logits(outputs), pngs)
             seen_batches += 1
             if max_batches is not None and seen_batches >= max_batches:
                 break
     tp, fp, fn, tn = (float(v) for v in conf.tolist())
     metrics = binary_segmentation_metrics(tp, fp, fn, tn)
     metrics["Loss"] = float(total_loss.item() / max(seen_batches, 1))
+    if bacc is not None:
+        metrics.update(bacc.metrics())
     return metrics
 
 
@@ -212,10 +226,12 @@ def train_one_epoch_multitask(model, optimizer, train_loader, device, criterion,
     return l, sl, cl, 100.0 * float(correct.item()) / max(total, 1)
 
 
-def evaluate_multitask(model, loader, device, criterion, max_batches=None):
+def evaluate_multitask(model, loader, device, criterion, max_batches=None, boundary=None):
     """train.py:294-355 / val.py:73-110: eval-mode forward; seg IoU = I/(U+1e-6), Dice = 2I/(|P|+|T|+1e-6)
-    with P = sigmoid(seg) > 0.5 (fused confusion kernel, u64 counts on the device); cls accuracy %."""
+    with P = sigmoid(seg) > 0.5 (fused confusion kernel, u64 counts on the device); cls accuracy %.
+    boundary: as in evaluate_binary, on the segmentation head."""
     model.eval()
+    bacc = _boundary_acc(boundary)
     sums = torch.zeros(3, dtype=torch.float64, device=device)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     correct = torch.zeros((), dtype=torch.int64, device=device)
@@ -230,14 +246,20 @@ def evaluate_multitask(model, loader, device, criterion, max_batches=None):
             loss, seg_loss, cls_loss = criterion(seg_logits, cls_logits, seg_targets, cls_targets)
             sums += torch.stack([loss, seg_loss, cls_loss]).double()
             losses.binary_confusion(seg_logits, seg_targets, conf)
+            if bacc is not None:
+                bacc.add(labels_from_logits(seg_logits), seg_targets)
             correct += cls_logits.argmax(1).eq(cls_targets).sum()
             total += cls_targets.size(0)
     tp, fp, fn, _tn = (float(v) for v in conf.tolist())
     losses.raise_if_soft_targets(device)
     n = max(len(loader), 1)
     l, sl, cl = (float(v) / n for v in sums.tolist())
-    return {"Loss": l, "Seg Loss": sl, "Cls Loss": cl, "IoU": tp / (tp + fp + fn + 1e-6),
-            "Dice": 2 * tp / ((tp + fp) + (tp + fn) + 1e-6), "Cls Acc": 100.0 * float(correct.item()) / max(total, 1)}
+    metrics = {"Loss": l, "Seg Loss": sl, "Cls Loss": cl, "IoU": tp / (tp + fp + fn + 1e-6),
+               "Dice": 2 * tp / ((tp + fp) + (tp + fn) + 1e-6),
+               "Cls Acc": 100.0 * float(correct.item()) / max(total, 1)}
+    if bacc is not None:
+        metrics.update(bacc.metrics())
+    return metrics
 
 
 # ------------------------------------------------------------------------------------------------
@@ -317,9 +339,13 @@ def train_one_epoch(model, optimizer, train_loader, device, dice_loss, focal_los
     return float(epoch_loss.item()) / max(n_batches, 1)
 
 
-def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lovasz_softmax=False):
-    """train_and_eval.py:411-513: per-batch metrics averaged over batches, as the reference does"""
+def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lovasz_softmax=False, boundary=None):
+    """train_and_eval.py:411-513: per-batch metrics averaged over batches, as the reference does.
+    boundary: None, or {"tolerance": px, "biou_d": px or None} to add the boundary metrics: counted over
+    the split per class 1 .. num_classes - 1 with num_classes as the ignored target value, each key the
+    mean over the classes with a target edge pixel (0.0 without one)."""
     import numpy as np
+    bacc = _boundary_acc(boundary, tuple(range(1, num_classes)), num_classes)
     weights = torch.tensor(np.ones([num_classes], np.float32)).to(device)
     model_eval = model.eval().to(device)
     hists, loss_sum = [], torch.zeros((), dtype=torch.float64, device=device)
@@ -330,6 +356,8 @@ def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lova
             loss_sum += _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss,
                                  lovasz_softmax).double()
             hists.append(losses.mc_confusion(outputs, pngs))
+            if bacc is not None:
+                bacc.add(labels_from_logits(outputs), pngs)
     n = max(len(val_loader), 1)
     keys = ("Pixel Accuracy", "Mean Accuracy", "Mean IoU", "Frequency Weighted IoU")
     tot = dict.fromkeys(keys, 0.0)
@@ -339,4 +367,6 @@ def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lova
             tot[k] += m[k]
     metrics = {k: tot[k] / n for k in keys}
     metrics["Loss"] = float(loss_sum.item()) / n
+    if bacc is not None:
+        metrics.update(bacc.metrics())
     return metrics

@@ -7,6 +7,9 @@ reference's `evaluate` (CE + Dice loss, pixel / mean accuracy, mean / frequency-
 Data: the HF parquet test split (utils/hf_dataloader.py, device augmentation) or the seeded
 synthetic test split (`--data-path synthetic`, binary / multitask only).
 
+`--boundary-metrics` adds boundary precision / recall / F1 at `--boundary-tolerance` pixels, Boundary
+IoU at `--boundary-iou-d` pixels and HD95 (unetseg_hip/boundary.py), printed after the usual lines.
+
 `--tta MODE` evaluates the model under flip / quarter-turn test-time augmentation
 (unetseg_hip/tta.py): the metrics and the reported loss are then computed on the merged
 log-probabilities, which stand in for the logits.
@@ -26,6 +29,8 @@ from torch.utils.data import DataLoader  # noqa: E402
 
 from model.model_factory import SUPPORTED_MODELS, build_model  # noqa: E402
 from unetseg_hip import losses  # noqa: E402
+from unetseg_hip.boundary import KEYS as BOUNDARY_KEYS, Accumulator as BoundaryAccumulator  # noqa: E402
+from unetseg_hip.boundary import labels_from_logits  # noqa: E402
 from unetseg_hip.tta import MODES as TTA_MODES, TTA  # noqa: E402
 from utils.hf_dataloader import DeviceLoader, HFUnetDataset, make_collate  # noqa: E402
 from utils.synthetic import SyntheticSegDataset, collate  # noqa: E402
@@ -34,7 +39,20 @@ from utils.train_and_eval import LogColor, evaluate, evaluate_binary  # noqa: E4
 CLASS_NAMES = ["动物类", "植物类", "复合类"]  # val.py:84
 
 
+def boundary_options(args):
+    """the `boundary` argument of the evaluate loops from the flags; None without --boundary-metrics"""
+    if not args.boundary_metrics:
+        return None
+    return {"tolerance": args.boundary_tolerance, "biou_d": args.boundary_iou_d or None}
+
+
+def print_boundary(m):
+    print("\t".join(f"{LogColor.RED}{k}{LogColor.RESET}" for k in BOUNDARY_KEYS))
+    print("\t".join(f"{m[k]:.4f}" for k in BOUNDARY_KEYS))
+
+
 def val(args):
+    boundary = boundary_options(args)
     num_classes = args.num_classes + 1 if args.task == "multiclass" else 2  # val.py:22-27
     device = torch.device(args.device)
     input_shape = [args.input_size] * 2
@@ -62,18 +80,24 @@ def val(args):
         model = TTA(model, args.tta)
 
     if args.task == "binary":
-        m = evaluate_binary(model, loader, device, loss_name=args.loss, pos_weight=None, ignore_index=None)
+        m = evaluate_binary(model, loader, device, loss_name=args.loss, pos_weight=None, ignore_index=None,
+                            boundary=boundary)
         print(f"{LogColor.RED}Dice{LogColor.RESET}\t{LogColor.RED}IoU{LogColor.RESET}\t{LogColor.RED}Precision"
               f"{LogColor.RESET}\t{LogColor.RED}Recall{LogColor.RESET}\t{LogColor.RED}Accuracy{LogColor.RESET}")
         print(f"{m['Dice']:.4f}\t{m['IoU']:.4f}\t{m['Precision']:.4f}\t{m['Recall']:.4f}\t{m['Accuracy']:.4f}")
+        if boundary is not None:
+            print_boundary(m)
         return m
     if args.task == "multiclass":
         m = evaluate(model, loader, device, dice_loss=True, focal_loss=False, num_classes=num_classes,
-                     lovasz_softmax=args.loss == "lovasz_softmax")
-        print(m)
+                     lovasz_softmax=args.loss == "lovasz_softmax", boundary=boundary)
+        print({k: v for k, v in m.items() if k not in BOUNDARY_KEYS})
+        if boundary is not None:
+            print_boundary(m)
         return m
 
     model.eval()
+    bacc = None if boundary is None else BoundaryAccumulator(boundary)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     per_cls = torch.zeros(3, 2, dtype=torch.int64, device=device)  # [class][correct, count]
     with torch.no_grad():
@@ -81,6 +105,8 @@ def val(args):
             images, seg_t, cls_t = images.to(device), seg_t.to(device), cls_t.to(device)
             seg_logits, cls_logits = model(images)
             losses.binary_confusion(seg_logits, seg_t, conf)
+            if bacc is not None:
+                bacc.add(labels_from_logits(seg_logits), seg_t)
             pred = cls_logits.argmax(1)
             for c in range(3):
                 sel = cls_t == c
@@ -98,7 +124,11 @@ def val(args):
         if n:
             print(f"    {name}: {100.0 * c / n:.2f}% ({n} samples)")
     print("=" * 50)
-    return {"IoU": iou, "Dice": dice, "Cls Acc": acc}
+    m = {"IoU": iou, "Dice": dice, "Cls Acc": acc}
+    if bacc is not None:
+        m.update(bacc.metrics())
+        print_boundary(m)
+    return m
 
 
 def parse_args(argv=None):
@@ -123,6 +153,13 @@ def parse_args(argv=None):
                    help="test-time augmentation: average the probabilities over the mirror (hflip), the mirror and "
                         "the half turn (flips) or all eight flips and quarter turns (d4); the reported loss is then "
                         "computed on the merged log-probabilities, not on the model's logits")
+    p.add_argument("--boundary-metrics", action="store_true",
+                   help="also report boundary precision / recall / F1, Boundary IoU and HD95 (class 1; multiclass: "
+                        "the mean over the classes with a target edge)")
+    p.add_argument("--boundary-tolerance", default=2.0, type=float,
+                   help="pixel tolerance of boundary precision / recall / F1")
+    p.add_argument("--boundary-iou-d", default=0, type=int,
+                   help="Boundary-IoU band width in pixels; 0 = 2 %% of the image diagonal")
     return p.parse_args(argv)
 
 
