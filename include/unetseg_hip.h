@@ -195,7 +195,10 @@ int unetseg_stem_fwd(const void* xp, int n, int h, int w, const void* wk, int K,
 size_t unetseg_stem_wgrad_workspace(int n, int h, int w, int K);
 int unetseg_stem_wgrad(const void* xp, int n, int h, int w, const void* dy, int ldy, int K, float* ws,
                        size_t ws_bytes, float* dw, int C, int accumulate, void* stream);
-/* NCHW fp32 input [n][c][h][w] -> NHWC dtype [n][h][w][cpad] (zero channel padding) */
+/* NCHW fp32 input [n][c][h][w] -> NHWC dtype [n][h][w][cpad] (zero channel padding), 1 <= c <= cpad.  Both packers
+ * read and write dense arrays, write exactly the stated extent (pack_input_stem: the 3 left and 5 right border
+ * columns and the channels >= c as zeros, 1 <= c <= 8) and return 0 without a launch, writing nothing, when n, h or
+ * w is 0. */
 int unetseg_pack_input(int dtype, const float* x, int n, int c, int h, int w, int cpad, void* y, void* stream);
 
 /* ---- BatchNorm2d, training and eval (model/resnet_backbone.py:127,169; model/unet_plain.py:10,13;
@@ -308,30 +311,72 @@ int unetseg_pad2d_bwd(int dtype, const void* dy, int ldy, int n, int h, int w, i
                       int ow, void* dx, int ldx, int accumulate, void* stream);
 
 /* ---- narrow 1x1 heads (final / outc / seg_head / psi: model/unet_resnet.py:78,
- *      model/unet_plain.py:69, model/unet_multitask.py:69, model/unet_attention.py:24) ------------ */
+ *      model/unet_plain.py:69, model/unet_multitask.py:69, model/unet_attention.py:24) ------------
+ *
+ * The pointwise contract (tests/test_gpu_pointwise_contract.py holds every entry point named here to it, element
+ * by element; tests/test_pointwise_args_cpu.py the refusals).  It covers unetseg_pw_small_fwd / _bwd / _bwd_relu,
+ * unetseg_pw_head_fwd / _bwd, unetseg_attn_apply / _bwd1 / _bwd2, unetseg_gap_fwd / _bwd and the two input packers.
+ *  - Strides: every NHWC operand (x, dx, skip, gated, dg, dskip, f, dzf) is a channel slice [c0, c0 + c) of a buffer
+ *    whose pixels are `ld` elements apart, each operand with its own ld >= c; the call passes the address of channel
+ *    c0 of the first pixel.  An ld below c is refused.  Everything else is dense: weights, biases, the planar fp32
+ *    images y / dy [n][k][hw] (M = n * hw), the per-pixel fp32 vectors psi, alpha, dpsibn [M], the BatchNorm scalars
+ *    and the partial arrays.
+ *  - Alignment: the kernels move 16-byte vectors (V = 8 bf16 / 4 fp32 elements), so c, every ld and every c0 are
+ *    multiples of V and the buffer's base is 16-byte aligned; an ld that is no multiple of V is refused.  The
+ *    exceptions access by element and take any ld >= c and any c0: unetseg_pw_head_bwd (c divides 256),
+ *    unetseg_gap_fwd / _bwd (any c > 0).
+ *  - Writes: no byte outside channels [c0, c0 + c) of the M pixels of an output, and nothing past the stated length
+ *    of a dense output, is written; no input is written.  Written outputs (y, stats, alpha, gated, dpsibn, dzf, g,
+ *    every partial array, dx / dskip without the accumulate flag) need no initialisation; with dx_acc / ds_acc /
+ *    accumulate != 0 the old value is read and the sum stored (one more rounding).  A NULL dx (pw_small_bwd,
+ *    pw_head_bwd) skips dx; lddx is then ignored.
+ *  - Aliasing: no output may overlap an input or another output of the same call.  Two inputs may be the same
+ *    buffer, and two operands may be disjoint channel slices of one buffer (the op layer's concat and dense-block
+ *    slices).
+ *  - Partials: one slot per pixel tile g, the sum over that tile's pixels [g * tile, min(M, (g + 1) * tile)), plainly
+ *    stored (never accumulated), to be summed over g by unetseg_colsum_finalize / unetseg_bn_bwd_finalize:
+ *      pw_small_bwd / _bwd_relu  part_w [k][c][G], part_b [k][G], part_d [G][2][c];  G = unetseg_pw_small_tiles(M),
+ *                                tile = unetseg_pw_small_tile(M)
+ *      pw_small_fwd              stats [G][2] = (sum, M2 about the tile's own mean) of y, the same G and tile
+ *      pw_head_bwd               part_w [k][c][G], part_b [k][G];  G = unetseg_pw_head_tiles(M), tile = 2048
+ *      attn_bwd1                 part [2][G1];  G1 = unetseg_attn_bwd1_tiles(M), tile = 128
+ *      attn_bwd2                 part_w [c][G], part_b [G];  G and tile as pw_small_bwd
+ *  - M == 0 (gap: B == 0, gap_bwd also HW == 0; the packers: n, h or w == 0) returns 0 and launches nothing; no
+ *    pointer is looked at.  Otherwise every pointer not marked "may be NULL" is required and NULL is refused.
+ *    Negative sizes, and hw <= 0 with M > 0, are refused. */
 int unetseg_pw_small_tile(long M); /* pixels per tile (2048, smaller when M gives < 512 tiles) */
 int unetseg_pw_small_tiles(long M);
-/* y fp32 planar [n][k][hw] (k <= 2); stats (k == 1, may be NULL) [unetseg_pw_small_tiles(M)][2] */
+/* y fp32 planar [n][k][hw] = x . W^T + b, k = 1 or 2, W fp32 [k][c], b fp32 [k] (may be NULL: no bias); c / V a power
+ * of two <= 64; stats (k == 1 only, may be NULL) [unetseg_pw_small_tiles(M)][2] */
 int unetseg_pw_small_fwd(int dtype, const void* x, int ldx, long M, int hw, int c, int k, const float* w,
                          const float* b, float* y, float* stats, void* stream);
+/* dx (may be NULL) (+)= dy . W; k = 1 or 2 (anything else is refused); c / V divides 256 */
 int unetseg_pw_small_bwd(int dtype, const float* dy, const void* x, int ldx, long M, int hw, int c, int k,
                          const float* w, void* dx, int lddx, int dx_acc, float* part_w, float* part_b, void* stream);
 /* pw_small_bwd with the producer ReLU's backward fused (x = ReLU output, sole consumer; bf16):
- * dx = (x > 0) ? dy.W : 0; part_d [G][2][c], slot 0 = column sums of dx (replaces the
+ * dx = (x > 0) ? dy.W : 0 (written, exactly 0 where x <= 0); part_d [G][2][c], slot 0 = column sums of the stored
+ * (rounded) dx, slot 1 = 0 (replaces the
  * reference autograd's ReLU backward + conv bias grad of up_conv's last conv, model/unet_resnet.py:70-78,100-103). */
 int unetseg_pw_small_bwd_relu(int dtype, const float* dy, const void* x, int ldx, long M, int hw, int c, int k,
                               const float* w, void* dx, int lddx, float* part_w, float* part_b, float* part_d,
                               void* stream);
 
 /* ---- attention gate (AttentionGate.forward: model/unet_attention.py:28-36) -------------------- */
-/* alpha = sigmoid(BN1(psi)); gated = skip * alpha */
+/* The pointwise contract above applies (strides lds_ / ldg / ldds / ldf / lddz, alignment, writes, M == 0).
+ * alpha [M] = sigmoid(psi * sc[0] + sh[0]) (fp32; within 4 fp32 ulps of the exact sigmoid of the fp32 argument);
+ * gated = skip * alpha; c a multiple of V */
 int unetseg_attn_apply(int dtype, const void* skip, int lds_, const float* psi, const float* sc, const float* sh,
                        float* alpha, void* gated, int ldg, long M, int c, void* stream);
-/* part: [2][G1] (sum dpsibn, sum dpsibn * xhat) per 128-pixel tile, G1 = unetseg_attn_bwd1_tiles(M) */
+/* dskip (+)= dg * alpha (ds_acc != 0 accumulates); dpsibn [M] = (sum_c dg * skip) * alpha * (1 - alpha), written;
+ * part: [2][G1] (sum dpsibn, sum dpsibn * xhat with xhat = (psi - mean[0]) * inv[0]) per 128-pixel tile,
+ * G1 = unetseg_attn_bwd1_tiles(M); c / V a power of two */
 int unetseg_attn_bwd1_tiles(long M);
 int unetseg_attn_bwd1(int dtype, const void* dg, int ldg, const void* skip, int lds_, const float* alpha,
                       const float* psi, const float* mean, const float* inv, void* dskip, int ldds, int ds_acc,
                       float* dpsibn, long M, int c, float* part, void* stream);
+/* dpsi = coef[0] * (dpsibn - coef[1] - xhat * coef[2]) (coef: the first three of unetseg_bn_bwd_finalize's table);
+ * dzf = (f > 0) ? dpsi * wpsi : 0, written, exactly 0 where f <= 0 (f = the ReLU output psi's conv read);
+ * part_w [c][G] = sum dpsi * f, part_b [G] = sum dpsi per tile of unetseg_pw_small_tile(M) pixels; c / V divides 256 */
 int unetseg_attn_bwd2(int dtype, const float* dpsibn, const float* psi, const float* mean, const float* inv,
                       const float* coef, const void* f, int ldf, const float* wpsi, void* dzf, int lddz, long M, int c,
                       float* part_w, float* part_b, void* stream);
@@ -376,7 +421,9 @@ int unetseg_scale_grad(const float* g, long n, const float* s1, float a1, const 
 int unetseg_pw_head_fwd(int dtype, const void* x, int ldx, long M, int hw, int c, int k, const float* w,
                         const float* b, float* y, void* stream);
 int unetseg_pw_head_tiles(long M);
-/* dx (may be NULL) (+)= dy . W; part_w [k][c][G], part_b [k][G] (G = unetseg_pw_head_tiles(M)); c divides 256 */
+/* dx (may be NULL) (+)= dy . W; part_w [k][c][G], part_b [k][G] (G = unetseg_pw_head_tiles(M), 2048-pixel tiles);
+ * c divides 256.  Both heads follow the pointwise contract stated with the narrow 1x1 heads above (pw_head_fwd
+ * moves 16-byte vectors: c and ldx multiples of V; pw_head_bwd accesses by element: any ldx, lddx >= c) */
 int unetseg_pw_head_bwd(int dtype, const float* dy, const void* x, int ldx, long M, int hw, int c, int k,
                         const float* w, void* dx, int lddx, int dx_acc, float* part_w, float* part_b, void* stream);
 size_t unetseg_mc_loss_workspace(int B, int C, long P);
@@ -523,6 +570,11 @@ int unetseg_stream_wait(void* waiter, void* signaler);
 int unetseg_stream_create_cumask(const unsigned* mask, int n_words, void** out);
 
 /* ---- multitask classification head (model/unet_multitask.py:73-80) -------------------------- */
+/* global average pooling over x NHWC [B][HW][C], a channel slice of pixel stride ldx >= C (accessed by element: any
+ * C > 0, ldx and c0): g fp32 [B][C] = the mean over the HW pixels (summed in double), written; its backward
+ * dx (+)= dg / HW at every pixel (accumulate != 0 adds onto dx).  B == 0 (gap_bwd: or HW == 0) returns 0 without a
+ * launch; gap_fwd refuses HW == 0 with B > 0 (a mean over no pixels).  Nothing outside channels [c0, c0 + C) of the
+ * B * HW pixels of dx, and nothing past g's B * C floats, is written. */
 int unetseg_gap_fwd(int dtype, const void* x, int ldx, int B, int HW, int C, float* g, void* stream);
 int unetseg_gap_bwd(int dtype, const float* dg, int B, int HW, int C, void* dx, int ldx, int accumulate,
                     void* stream);

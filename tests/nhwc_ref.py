@@ -1,6 +1,7 @@
 """Float64 references of the memory-bound NHWC operations (BatchNorm apply / backward, channel statistics,
-ReLU backward, add, column sums, max pool, bilinear x2 upsample, general bilinear resize, zero padding) and
-the helpers of the per-element contract tests (tests/test_gpu_elem_contract.py, test_gpu_resample_contract.py;
+ReLU backward, add, column sums, max pool, bilinear x2 upsample, general bilinear resize, zero padding, the
+narrow 1x1 heads, the attention gate, global average pooling, input packing) and the helpers of the per-element
+contract tests (tests/test_gpu_elem_contract.py, test_gpu_resample_contract.py, test_gpu_pointwise_contract.py;
 the references themselves are checked against PyTorch on the CPU in tests/test_nhwc_ref_cpu.py).
 
 Written from the text of include/unetseg_hip.h, in torch float64 on the CPU; nothing here imports the library
@@ -414,3 +415,194 @@ def pad2d(x, top, left, oh, ow):
         return g + f64(dx0), g.abs() + f64(dx0).abs(), 1
 
     return y, backward
+
+
+# ------------------------------------------------------------------------------------------------
+# narrow 1x1 heads (pw_small_*, pw_head_*): y planar [N][K][HW], x NHWC [M][C], M = N * HW
+# ------------------------------------------------------------------------------------------------
+#: one double-precision rounding in units of an fp32 rounding: a sum of n addends accumulated in double and cast
+#: to float once has k = 1 (the summand's own fp32 roundings) or 0, plus n * K_DOUBLE
+K_DOUBLE = 2.0 ** -29
+
+
+def tile_ranges(M, tile):
+    """[(p0, p1)] of the pixel tiles a kernel's grid runs: tile pixels each, the last one ragged"""
+    return [(p0, min(M, p0 + tile)) for p0 in range(0, M, tile)]
+
+
+def _planar(v, N):
+    """[M][K] -> planar [N][K][HW]"""
+    M, K = v.shape
+    return v.reshape(N, M // N, K).permute(0, 2, 1).contiguous()
+
+
+def _rows(v):
+    """planar [N][K][HW] -> [M][K]"""
+    N, K, HW = v.shape
+    return v.permute(0, 2, 1).reshape(N * HW, K)
+
+
+def pw_fwd(x, w, b, N):
+    """y[n][k][hw] = sum_c x[p][c] w[k][c] + b[k] (b may be None) -> (y, mag) planar [N][K][HW].
+    k = C + 2: C addends, their products rounded (a fused multiply-add saves that one), the bias add."""
+    x, w = f64(x), f64(w)
+    y, mag = x @ w.t(), x.abs() @ w.abs().t()
+    if b is not None:
+        y, mag = y + f64(b), mag + f64(b).abs()
+    return _planar(y, N), _planar(mag, N)
+
+
+def pw_bwd(dy, x, w, dx0, tile):
+    """Backward of pw_fwd over pixel tiles of `tile`: dy planar [N][K][HW], x [M][C], w [K][C], dx0 [M][C] or None.
+    -> dict: dx = dy . W (+ dx0) with dx_mag, k = K + 1 (+ 1 with dx0): K addends, rounded products, the add
+    onto dx0; part_w [K][C][G] = sum over the tile's pixels of dy[p][k] x[p][c] with part_w_mag, k = n + 1 (n
+    pixels of the tile, rounded products); part_b [K][G] = sum of dy[p][k] with part_b_mag, k = n; n [G]."""
+    g, x, w = _rows(f64(dy)), f64(x), f64(w)
+    M, C = x.shape
+    K = w.shape[0]
+    dx, dmag = g @ w, g.abs() @ w.abs()
+    if dx0 is not None:
+        dx, dmag = dx + f64(dx0), dmag + f64(dx0).abs()
+    tiles = tile_ranges(M, tile)
+    G = len(tiles)
+    pw, pwm = torch.zeros(K, C, G, dtype=F64), torch.zeros(K, C, G, dtype=F64)
+    pb, pbm = torch.zeros(K, G, dtype=F64), torch.zeros(K, G, dtype=F64)
+    for i, (p0, p1) in enumerate(tiles):
+        pw[:, :, i], pwm[:, :, i] = g[p0:p1].t() @ x[p0:p1], g[p0:p1].abs().t() @ x[p0:p1].abs()
+        pb[:, i], pbm[:, i] = g[p0:p1].sum(0), g[p0:p1].abs().sum(0)
+    return dict(dx=dx, dx_mag=dmag, part_w=pw, part_w_mag=pwm, part_b=pb, part_b_mag=pbm, n=[b - a for a, b in tiles])
+
+
+def tile_colsum(v, tile):
+    """v [M][C] -> (per-tile column sums [G][C], their magnitudes); k = n (the tile's pixels)"""
+    v = f64(v)
+    tiles = tile_ranges(v.shape[0], tile)
+    return (torch.stack([v[a:b].sum(0) for a, b in tiles]), torch.stack([v[a:b].abs().sum(0) for a, b in tiles]))
+
+
+def pw_bwd_relu(dy, x, w, tile, store_dtype):
+    """pw_bwd with the backward of the ReLU that produced x fused: -> pw_bwd's dict with
+    dx_pre = dy . W where x > 0, else 0 (the value before the store; its bound is pw_bwd's, k = K + 1, and
+    the zeros are exact), dx = round_store(dx_pre), part_d [G][2][C]: slot 0 the column sums of the *stored*
+    dx over the tile (k = n), slot 1 zero, with part_d_mag."""
+    out = pw_bwd(dy, x, w, None, tile)
+    pos = f64(x) > 0
+    zero = torch.zeros((), dtype=F64)
+    out["dx_pre"] = torch.where(pos, out["dx"], zero)
+    out["dx_mag"] = torch.where(pos, out["dx_mag"], zero)
+    out["dx"] = round_store(out["dx_pre"], store_dtype).to(F64)
+    s, m = tile_colsum(out["dx"], tile)
+    out["part_d"] = torch.stack([s, torch.zeros_like(s)], 1)
+    out["part_d_mag"] = torch.stack([m, torch.zeros_like(m)], 1)
+    return out
+
+
+def tile_stats(v, tile):
+    """v [M] (the fp32 psi a kernel stored) -> (part [G][2] = (sum, M2 about the tile mean), mag [G][2], n [G]).
+    Accumulated in double from the stored fp32 values and cast once: k = n * K_DOUBLE (sum), (n + 3) * K_DOUBLE
+    (M2), each next to the store's own ulp."""
+    part, mag, n = channel_stats(f64(v).reshape(-1, 1), tile)
+    return part[:, :, 0], mag[:, :, 0], n
+
+
+# ------------------------------------------------------------------------------------------------
+# attention gate: alpha = sigmoid(psi * sc + sh), gated = skip * alpha, and its backward
+# ------------------------------------------------------------------------------------------------
+def attn_alpha(psi, sc, sh):
+    """-> (alpha = sigmoid(z), z = psi * sc + sh, mag of z) in float64"""
+    psi, sc, sh = f64(psi), f64(sc).reshape(()), f64(sh).reshape(())
+    z = psi * sc + sh
+    return torch.sigmoid(z), z, (psi * sc).abs() + sh.abs()
+
+
+def attn_apply(skip, alpha):
+    """gated[p][c] = skip[p][c] alpha[p] -> (value, mag); k = 1 (one product)"""
+    v = f64(skip) * f64(alpha).unsqueeze(-1)
+    return v, v.abs()
+
+
+def attn_bwd1(dg, skip, alpha, ds0=None):
+    """-> dict: dskip = dg alpha (+ ds0) with dskip_mag, k = 1 (+ 1 with ds0; a fused multiply-add saves it);
+    dpsibn[p] = (sum_c dg skip) alpha (1 - alpha) with dpsibn_mag, k = C + 4: C addends, rounded products,
+    the product with alpha, 1 - alpha, the product with it."""
+    dg, skip, al = f64(dg), f64(skip), f64(alpha)
+    ds = dg * al.unsqueeze(-1)
+    dsm = ds.abs()
+    if ds0 is not None:
+        ds, dsm = ds + f64(ds0), dsm + f64(ds0).abs()
+    s = al * (1 - al)
+    return dict(dskip=ds, dskip_mag=dsm, dpsibn=(dg * skip).sum(-1) * s, dpsibn_mag=(dg * skip).abs().sum(-1) * s)
+
+
+def attn_bwd1_part(dpsibn, psi, mean, inv, tile=128):
+    """per-tile partials [2][G1] of the psi BatchNorm's backward from the stored fp32 dpsibn: sum of dpsibn, sum of
+    dpsibn * xhat with xhat = (psi - mean) * inv -> (part, mag, n [G1]).  Accumulated in double: k = n * K_DOUBLE
+    for the first; the second forms psi - mean in fp32: k = 1 + n * K_DOUBLE."""
+    d, psi, mean, inv = f64(dpsibn), f64(psi), f64(mean).reshape(()), f64(inv).reshape(())
+    t = d * ((psi - mean) * inv)
+    tiles = tile_ranges(d.shape[0], tile)
+    part = torch.stack([torch.stack([d[a:b].sum() for a, b in tiles]), torch.stack([t[a:b].sum() for a, b in tiles])])
+    mag = torch.stack([torch.stack([d[a:b].abs().sum() for a, b in tiles]),
+                       torch.stack([t[a:b].abs().sum() for a, b in tiles])])
+    return part, mag, [b - a for a, b in tiles]
+
+
+K_ATTN_DPSI = 5  # psi - mean, * inv, dpsibn - coef1, the multiply-add with coef2, * coef0
+
+
+def attn_bwd2(dpsibn, psi, mean, inv, coef, f, wpsi, tile):
+    """dpsi = coef0 (dpsibn - coef1 - xhat coef2) (k = K_ATTN_DPSI); dzf[p][c] = dpsi[p] wpsi[c] where f > 0, else 0
+    (k = K_ATTN_DPSI + 1); part_w [C][G] = sum over the tile's pixels of dpsi f (k = n + K_ATTN_DPSI); part_b [G] =
+    sum of dpsi (k = n + K_ATTN_DPSI) -> dict with the magnitudes and n [G]."""
+    d, psi, mean, inv, coef = f64(dpsibn), f64(psi), f64(mean).reshape(()), f64(inv).reshape(()), f64(coef).reshape(-1)
+    f, w = f64(f), f64(wpsi).reshape(-1)
+    xh = (psi - mean) * inv
+    dp = coef[0] * (d - coef[1] - xh * coef[2])
+    dpm = coef[0].abs() * (d.abs() + coef[1].abs() + (xh * coef[2]).abs())
+    pos = f > 0
+    zero = torch.zeros((), dtype=F64)
+    dzf = torch.where(pos, dp.unsqueeze(-1) * w, zero)
+    dzm = torch.where(pos, dpm.unsqueeze(-1) * w.abs(), zero)
+    tiles = tile_ranges(d.shape[0], tile)
+    pw = torch.stack([dp[a:b] @ f[a:b] for a, b in tiles], 1)
+    pwm = torch.stack([dpm[a:b] @ f[a:b].abs() for a, b in tiles], 1)
+    pb = torch.stack([dp[a:b].sum() for a, b in tiles])
+    pbm = torch.stack([dpm[a:b].sum() for a, b in tiles])
+    return dict(dpsi=dp, dpsi_mag=dpm, dzf=dzf, dzf_mag=dzm, part_w=pw, part_w_mag=pwm, part_b=pb, part_b_mag=pbm,
+                n=[b - a for a, b in tiles])
+
+
+# ------------------------------------------------------------------------------------------------
+# global average pooling, input packing
+# ------------------------------------------------------------------------------------------------
+def gap_fwd(x):
+    """x [B][HW][C] -> (g [B][C] = the mean over the pixels, mag).  Summed in double, divided in double, cast
+    once: k = (HW + 1) * K_DOUBLE next to the store's ulp."""
+    x = f64(x)
+    return x.mean(1), x.abs().mean(1)
+
+
+def gap_bwd(dg, HW, dx0=None):
+    """dx[b][p][c] = dg[b][c] / HW (+ dx0) -> (value [B][HW][C], mag); k = 1 (the division), + 1 with dx0"""
+    v = (f64(dg) / HW).unsqueeze(1).expand(-1, HW, -1).clone()
+    m = v.abs()
+    if dx0 is not None:
+        v, m = v + f64(dx0), m + f64(dx0).abs()
+    return v, m
+
+
+def pack_input(x, cpad, store_dtype):
+    """NCHW fp32 [N][C][H][W] -> NHWC [N][H][W][cpad] in the storage type, channels >= C zero: exact"""
+    N, C, H, W = x.shape
+    y = torch.zeros(N, H, W, cpad, dtype=store_dtype)
+    y[..., :C] = x.detach().cpu().permute(0, 2, 3, 1).to(torch.float32).to(store_dtype)
+    return y
+
+
+def pack_input_stem(x):
+    """NCHW fp32 [N][C][H][W], C <= 8 -> bf16 [N][H][W + 8][8]: image column w at packed column w + 3, the 3 left
+    and 5 right border columns and the channels >= C zero: exact"""
+    N, C, H, W = x.shape
+    y = torch.zeros(N, H, W + 8, 8, dtype=torch.bfloat16)
+    y[:, :, 3:3 + W, :C] = x.detach().cpu().permute(0, 2, 3, 1).to(torch.float32).to(torch.bfloat16)
+    return y

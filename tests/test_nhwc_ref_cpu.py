@@ -288,3 +288,138 @@ def test_sliced_and_guard(dtype, fill):
     flat[32] = 0
     with pytest.raises(AssertionError):
         R.assert_tail(flat, 32, 0xEE)
+
+
+# ---- narrow 1x1 heads, attention gate, global average pooling, input packing --------------------
+@pytest.mark.parametrize("K", [1, 2, 3])
+def test_pw_heads(K):
+    """pw_fwd / pw_bwd / pw_bwd_relu against F.conv2d (1x1) and its autograd: the value, dx (plain, accumulated and
+    through the producer's ReLU) and the per-tile partials, which sum to the parameter gradients and of which
+    the ragged last tile (one pixel) is that pixel's own outer product"""
+    g = _gen(40 + K)
+    N, HW, C, tile = 3, 43, 8, 128
+    M = N * HW
+    a = torch.randn(N, C, HW, 1, generator=g, dtype=F64).requires_grad_()
+    w = torch.randn(K, C, generator=g, dtype=F64).requires_grad_()
+    b = torch.randn(K, generator=g, dtype=F64).requires_grad_()
+    dy = torch.randn(N, K, HW, generator=g, dtype=F64)
+    xin = torch.relu(a)
+    xin.retain_grad()
+    want = F.conv2d(xin, w.view(K, C, 1, 1), b)
+    (want[..., 0] * dy).sum().backward()
+    x = xin.detach()[..., 0].permute(0, 2, 1).reshape(M, C)
+    y, mag = R.pw_fwd(x, w, b, N)
+    assert y.shape == (N, K, HW)
+    _close(y, want.detach()[..., 0], "pw_fwd")
+    assert bool((mag >= y.abs() * (1 - 1e-12)).all())
+    _close(R.pw_fwd(x, w, None, N)[0], want.detach()[..., 0] - b.detach().view(1, K, 1), "pw_fwd without bias")
+    o = R.pw_bwd(dy, x, w, None, tile)
+    nhwc = lambda t: t[..., 0].permute(0, 2, 1).reshape(M, C)
+    _close(o["dx"], nhwc(xin.grad), "pw_bwd dx")
+    assert o["n"] == [128, 1] and o["part_w"].shape == (K, C, 2) and o["part_b"].shape == (K, 2)
+    _close(o["part_w"].sum(-1), w.grad, "part_w summed over the tiles")
+    _close(o["part_b"].sum(-1), b.grad, "part_b summed over the tiles")
+    last = dy.permute(0, 2, 1).reshape(M, K)[M - 1]
+    _close(o["part_w"][:, :, 1], last.view(K, 1) * x[M - 1].view(1, C), "part_w of the one-pixel tile")
+    _close(o["part_b"][:, 1], last, "part_b of the one-pixel tile")
+    dx0 = torch.randn(M, C, generator=g, dtype=F64)
+    oa = R.pw_bwd(dy, x, w, dx0, tile)
+    _close(oa["dx"], nhwc(xin.grad) + dx0, "pw_bwd dx accumulated")
+    assert bool((oa["dx_mag"] >= oa["dx"].abs() * (1 - 1e-12)).all())
+    r = R.pw_bwd_relu(dy, x, w, tile, torch.bfloat16)
+    _close(r["dx_pre"], nhwc(a.grad), "pw_bwd_relu dx before the store")
+    assert torch.equal(r["dx"], R.round_store(r["dx_pre"], torch.bfloat16).to(F64))
+    assert bool((r["dx"][x <= 0] == 0).all()) and int((x <= 0).sum()) > 0
+    assert r["part_d"].shape == (2, 2, C) and bool((r["part_d"][:, 1] == 0).all())
+    _close(r["part_d"][:, 0].sum(0), r["dx"].sum(0), "part_d slot 0 summed over the tiles")
+    _close(r["part_d"][1, 0], r["dx"][M - 1], "part_d of the one-pixel tile")
+    _close(r["part_w"], o["part_w"], "pw_bwd_relu part_w")
+
+
+def test_attention_gate():
+    """the gate's references chained as the op layer chains the kernels, against an autograd restatement of
+    model/unet_attention.py:30-35 from the ReLU on: f = relu(pre), psi = BN(conv1x1(f)) with batch statistics,
+    alpha = sigmoid(psi), out = skip * alpha"""
+    g = _gen(77)
+    M, Ci, Cs, tile, eps = 301, 8, 12, 128, 1e-5
+    pre = torch.randn(M, Ci, generator=g, dtype=F64).requires_grad_()
+    skip = torch.randn(M, Cs, generator=g, dtype=F64).requires_grad_()
+    w = torch.randn(1, Ci, generator=g, dtype=F64).requires_grad_()
+    b = torch.randn(1, generator=g, dtype=F64).requires_grad_()
+    gam = torch.tensor([1.3], dtype=F64, requires_grad=True)
+    bet = torch.tensor([0.2], dtype=F64, requires_grad=True)
+    dg = torch.randn(M, Cs, generator=g, dtype=F64)
+    ds0 = torch.randn(M, Cs, generator=g, dtype=F64)
+    f = torch.relu(pre)
+    lin = f @ w.t() + b
+    bn = F.batch_norm(lin.t().reshape(1, 1, M), None, None, gam, bet, True, 0.1, eps).reshape(M)
+    al = torch.sigmoid(bn)
+    out = skip * al.unsqueeze(1)
+    (out * dg).sum().backward()
+    # forward chain
+    fd = f.detach()
+    psi = R.pw_fwd(fd, w, b, 1)[0].reshape(M)
+    _close(psi, lin.detach().reshape(M), "psi")
+    part, pmag, ns = R.tile_stats(psi, tile)
+    assert ns == [128, 128, 45] and part.shape == (3, 2)
+    cnt = torch.tensor(ns, dtype=F64)
+    mean = part[:, 0].sum() / M
+    var = (part[:, 1] + cnt * (part[:, 0] / cnt - mean) ** 2).sum() / M
+    _close(mean, psi.mean(), "merged mean of psi")
+    _close(var, psi.var(unbiased=False), "merged variance of psi")
+    fin = R.bn_finalize(mean.reshape(1), var.reshape(1), M, gam, bet, torch.zeros(1), torch.ones(1), 0.1, eps)
+    alpha, z, zmag = R.attn_alpha(psi, fin["scale"], fin["shift"])
+    _close(alpha, al.detach(), "alpha")
+    assert bool((zmag >= z.abs() * (1 - 1e-12)).all())
+    gated, gmag = R.attn_apply(skip.detach(), alpha)
+    _close(gated, out.detach(), "gated")
+    # backward chain
+    b1 = R.attn_bwd1(dg, skip.detach(), alpha)
+    _close(b1["dskip"], skip.grad, "dskip")
+    _close(R.attn_bwd1(dg, skip.detach(), alpha, ds0)["dskip"], skip.grad + ds0, "dskip accumulated")
+    p1, p1mag, n1 = R.attn_bwd1_part(b1["dpsibn"], psi, fin["mean"], fin["invstd"])
+    assert p1.shape == (2, 3) and n1 == ns
+    _close(p1[0].sum(), bet.grad[0], "sum dpsibn = dbeta")
+    _close(p1[1].sum(), gam.grad[0], "sum dpsibn xhat = dgamma")
+    coef = torch.stack([gam.detach()[0] * fin["invstd"][0], p1[0].sum() / M, p1[1].sum() / M])
+    b2 = R.attn_bwd2(b1["dpsibn"], psi, fin["mean"], fin["invstd"], coef, fd, w, tile)
+    _close(b2["dzf"], pre.grad, "dzf (through the ReLU)")
+    assert bool((b2["dzf"][fd <= 0] == 0).all())
+    assert b2["part_w"].shape == (Ci, 3) and b2["part_b"].shape == (3,) and b2["n"] == ns
+    _close(b2["part_w"].sum(1), w.grad[0], "part_w summed over the tiles")
+    # the bias in front of a batch-statistics BN has a zero gradient: hold the sum to its terms' magnitude
+    assert abs(float(b2["part_b"].sum()) - float(b.grad[0])) <= 1e-12 * float(b2["dpsi"].abs().sum())
+    _close(b2["part_w"][:, 2], b2["dpsi"][256:] @ fd[256:], "part_w of the ragged tile")
+    for k in ("dpsi", "dzf", "part_w", "part_b"):
+        assert bool((b2[k + "_mag"] >= b2[k].abs() * (1 - 1e-12)).all()), k
+
+
+@pytest.mark.parametrize("B,HW,C", [(1, 1, 1), (3, 7, 8), (2, 300, 5)])
+def test_gap(B, HW, C):
+    g = _gen(B * 1000 + HW)
+    x = torch.randn(B, HW, C, generator=g, dtype=F64).requires_grad_()
+    dgp = torch.randn(B, C, generator=g, dtype=F64)
+    (x.mean(1) * dgp).sum().backward()
+    v, m = R.gap_fwd(x)
+    _close(v, x.detach().mean(1), "gap_fwd")
+    assert bool((m >= v.abs() * (1 - 1e-12)).all())
+    _close(R.gap_bwd(dgp, HW)[0], x.grad, "gap_bwd")
+    dx0 = torch.randn(B, HW, C, generator=g, dtype=F64)
+    va, ma = R.gap_bwd(dgp, HW, dx0)
+    _close(va, x.grad + dx0, "gap_bwd accumulated")
+    assert bool((ma >= va.abs() * (1 - 1e-12)).all())
+
+
+@pytest.mark.parametrize("c,cpad", [(1, 1), (3, 8), (4, 16)])
+def test_pack_input(c, cpad):
+    g = _gen(c + cpad)
+    x = torch.randn(2, c, 3, 5, generator=g)
+    for dt in (torch.float32, torch.bfloat16):
+        y = R.pack_input(x, cpad, dt)
+        assert y.shape == (2, 3, 5, cpad) and y.dtype == dt
+        assert torch.equal(y[..., :c], _nhwc(x).to(dt)) and bool((y[..., c:] == 0).all())
+    if c <= 8:
+        s = R.pack_input_stem(x)
+        assert s.shape == (2, 3, 13, 8) and s.dtype == torch.bfloat16
+        assert torch.equal(s[:, :, 3:8, :c], _nhwc(x).to(torch.bfloat16))
+        assert bool((s[:, :, :3] == 0).all()) and bool((s[:, :, 8:] == 0).all()) and bool((s[..., c:] == 0).all())

@@ -174,7 +174,9 @@ __global__ void ce_kernel(const float* logits, const int64_t* tgt, int B, int K,
 // =========================================================================================
 UNETSEG_API int unetseg_gap_fwd(int dtype, const void* x, int ldx, int B, int HW, int C, float* g, void* stream) {
   US_CHECK_DTYPE(dtype, "gap_fwd");
-  US_CHECK_ARG(x && g && B > 0 && HW > 0 && C > 0 && ldx >= C, "gap_fwd: bad args");
+  US_CHECK_ARG(B >= 0 && HW > 0 && C > 0 && ldx >= C, "gap_fwd: bad sizes (B=%d HW=%d C=%d; ldx=%d must be at least C)", B, HW, C, ldx);
+  if (B == 0) return 0;
+  US_CHECK_ARG(x && g, "gap_fwd: null pointer");
   DISPATCH_T(dtype, hipLaunchKernelGGL(gap_kernel<T>, dim3(ceil_div(B * C, 256)), dim3(256), 0, (hipStream_t)stream,
                                        (const T*)x, ldx, B, HW, C, g));
   US_LAUNCH_CHECK("gap_fwd");
@@ -184,7 +186,9 @@ UNETSEG_API int unetseg_gap_fwd(int dtype, const void* x, int ldx, int B, int HW
 UNETSEG_API int unetseg_gap_bwd(int dtype, const float* dg, int B, int HW, int C, void* dx, int ldx, int accumulate,
                                 void* stream) {
   US_CHECK_DTYPE(dtype, "gap_bwd");
-  US_CHECK_ARG(dg && dx && B > 0 && HW > 0 && C > 0 && ldx >= C, "gap_bwd: bad args");
+  US_CHECK_ARG(B >= 0 && HW >= 0 && C > 0 && ldx >= C, "gap_bwd: bad sizes (B=%d HW=%d C=%d; ldx=%d must be at least C)", B, HW, C, ldx);
+  if ((long)B * HW == 0) return 0;
+  US_CHECK_ARG(dg && dx, "gap_bwd: null pointer");
   const long n = (long)B * HW * C;
   DISPATCH_T(dtype, hipLaunchKernelGGL(gap_bwd_kernel<T>, dim3(grid_for(n, 8192)), dim3(256), 0,
                                        (hipStream_t)stream, dg, B, HW, C, (T*)dx, ldx, accumulate));

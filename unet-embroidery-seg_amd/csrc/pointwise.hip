@@ -606,6 +606,18 @@ void pw_small_dispatch_k(int k, F&& f) {
 
 }  // namespace
 
+// The argument checks shared by the strided entry points below (include/unetseg_hip.h, "the pointwise
+// contract").  Sizes and strides are checked first, then M == 0 returns 0 (nothing to do, no launch, no
+// pointer looked at), then the required pointers.
+// ld (elements between pixels) of an operand the kernel reads or writes in 16-B vectors
+#define CHECK_LD_VEC(dtype, ld, c, name, what)                                                                  \
+  US_CHECK_ARG((ld) >= (c) && (ld) % vec_elems(dtype) == 0,                                                     \
+               "%s: %s (%d) must be at least c (%d) and a multiple of the 16-B vector", name, what, (int)(ld),  \
+               (int)(c))
+// M pixels in planar images of hw pixels
+#define CHECK_PIXELS(M, hw, name) \
+  US_CHECK_ARG((M) >= 0 && ((M) == 0 || (hw) > 0), "%s: bad pixel counts (M=%ld, hw=%d)", name, (long)(M), (int)(hw))
+
 // =========================================================================================
 // C ABI
 // =========================================================================================
@@ -613,6 +625,7 @@ UNETSEG_API int unetseg_pack_input(int dtype, const float* x, int n, int c, int 
                                    void* stream) {
   US_CHECK_DTYPE(dtype, "pack_input");
   US_CHECK_ARG(cpad >= c && c > 0 && n >= 0 && h >= 0 && w >= 0, "pack_input: bad sizes (c=%d, cpad=%d < c?)", c, cpad);
+  if ((long)n * h * w == 0) return 0;
   US_CHECK_ARG(x && y, "pack_input: null pointer");
   DISPATCH_T(dtype, hipLaunchKernelGGL(pack_input_kernel<T>, dim3(grid_for((long)n * h * w)), dim3(256), 0,
                                        (hipStream_t)stream, x, n, c, h, w, cpad, (T*)y));
@@ -643,7 +656,10 @@ __global__ void pack_input_stem_kernel(const float* x, int N, int C, int H, int 
 }
 
 UNETSEG_API int unetseg_pack_input_stem(const float* x, int n, int c, int h, int w, void* y, void* stream) {
-  US_CHECK_ARG(x && y && c >= 1 && c <= 8, "pack_input_stem: bad args");
+  US_CHECK_ARG(c >= 1 && c <= 8 && n >= 0 && h >= 0 && w >= 0, "pack_input_stem: bad sizes (n=%d c=%d h=%d w=%d, 1 <= c <= 8)",
+               n, c, h, w);
+  if ((long)n * h * w == 0) return 0;  // an empty image: nothing is written, the border columns included
+  US_CHECK_ARG(x && y, "pack_input_stem: null pointer");
   hipLaunchKernelGGL(pack_input_stem_kernel, dim3(grid_for((long)n * h * (w + 8))), dim3(256), 0, (hipStream_t)stream,
                      x, n, c, h, w, (bf16*)y);
   US_LAUNCH_CHECK("pack_input_stem");
@@ -670,6 +686,10 @@ UNETSEG_API int unetseg_pw_small_fwd(int dtype, const void* x, int ldx, long M, 
   US_CHECK_ARG(cv <= 64 && (cv & (cv - 1)) == 0, "pw_small_fwd: C/V must be a power of two <= 64");
   US_CHECK_ARG(k == 1 || k == 2, "pw_small_fwd: k must be 1 or 2");
   US_CHECK_ARG(!stats || k == 1, "pw_small_fwd: stats only for k==1");
+  CHECK_LD_VEC(dtype, ldx, c, "pw_small_fwd", "ldx");
+  CHECK_PIXELS(M, hw, "pw_small_fwd");
+  if (M == 0) return 0;
+  US_CHECK_ARG(x && w && y, "pw_small_fwd: null pointer (x, w and y are required)");
   // without statistics the tile only sets the grid (every pixel's output is its own): 128-pixel blocks,
   // twice the resident waves of pw_tile's for the latency-bound head -- the attention U-Net's 64 -> 2
   // head at 8 x 512^2: 105.6 (2048) / 95.7 (512) / 87.7 (256) / 82.0 us (128).  UNETSEG_PW_FWD_TILE = T
@@ -695,6 +715,12 @@ UNETSEG_API int unetseg_pw_small_bwd(int dtype, const float* dy, const void* x, 
   CHECK_VEC(dtype, c, "pw_small_bwd");
   const int cv = c / vec_elems(dtype);
   US_CHECK_ARG(cv <= 256 && 256 % cv == 0, "pw_small_bwd: bad C");
+  US_CHECK_ARG(k == 1 || k == 2, "pw_small_bwd: k must be 1 or 2");
+  CHECK_LD_VEC(dtype, ldx, c, "pw_small_bwd", "ldx");
+  if (dx) CHECK_LD_VEC(dtype, lddx, c, "pw_small_bwd", "lddx");
+  CHECK_PIXELS(M, hw, "pw_small_bwd");
+  if (M == 0) return 0;
+  US_CHECK_ARG(dy && x && w && part_w && part_b, "pw_small_bwd: null pointer (only dx may be NULL)");
   const int G = unetseg_pw_small_tiles(M);
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_T(dtype, pw_small_dispatch_k(k, [&](auto kc) {
@@ -715,7 +741,12 @@ UNETSEG_API int unetseg_pw_small_bwd_relu(int dtype, const float* dy, const void
   CHECK_VEC(dtype, c, "pw_small_bwd_relu");
   US_CHECK_ARG(c / 8 <= 256 && 256 % (c / 8) == 0, "pw_small_bwd_relu: bad C");
   US_CHECK_ARG(k == 1 || k == 2, "pw_small_bwd_relu: k must be 1 or 2");
+  CHECK_LD_VEC(dtype, ldx, c, "pw_small_bwd_relu", "ldx");
+  CHECK_LD_VEC(dtype, lddx, c, "pw_small_bwd_relu", "lddx");
+  CHECK_PIXELS(M, hw, "pw_small_bwd_relu");
+  if (M == 0) return 0;
   US_CHECK_ARG(dx != nullptr && part_d != nullptr, "pw_small_bwd_relu: dx and part_d required");
+  US_CHECK_ARG(dy && x && w && part_w && part_b, "pw_small_bwd_relu: null pointer");
   const int G = unetseg_pw_small_tiles(M);
   hipStream_t st = (hipStream_t)stream;
   pw_small_dispatch_k(k, [&](auto kc) {
@@ -730,9 +761,13 @@ UNETSEG_API int unetseg_pw_head_tiles(long M) { return ceil_div(M, (long)kHeadTi
 
 UNETSEG_API int unetseg_pw_head_fwd(int dtype, const void* x, int ldx, long M, int hw, int c, int k, const float* w,
                                     const float* b, float* y, void* stream) {
-  US_CHECK_ARG(x && w && y && k >= 1 && k <= kMaxC && c > 0 && c % vec_elems(dtype) == 0,
+  US_CHECK_DTYPE(dtype, "pw_head_fwd");
+  US_CHECK_ARG(k >= 1 && k <= kMaxC && c > 0 && c % vec_elems(dtype) == 0,
                "pw_head_fwd: bad args (k=%d <= %d, c=%d multiple of the 16-B vector)", k, kMaxC, c);
-  if (M <= 0) return 0;
+  CHECK_LD_VEC(dtype, ldx, c, "pw_head_fwd", "ldx");
+  CHECK_PIXELS(M, hw, "pw_head_fwd");
+  if (M == 0) return 0;
+  US_CHECK_ARG(x && w && y, "pw_head_fwd: null pointer (x, w and y are required)");
   const size_t lds = (size_t)k * c * sizeof(float);
   DISPATCH_T(dtype, hipLaunchKernelGGL(pw_head_fwd_kernel<T>, dim3(ceil_div(M, 256)), dim3(256), lds,
                                        (hipStream_t)stream, (const T*)x, ldx, M, hw, c, k, w, b, y));
@@ -744,9 +779,14 @@ UNETSEG_API int unetseg_pw_head_fwd(int dtype, const void* x, int ldx, long M, i
 UNETSEG_API int unetseg_pw_head_bwd(int dtype, const float* dy, const void* x, int ldx, long M, int hw, int c, int k,
                                     const float* w, void* dx, int lddx, int dx_acc, float* part_w, float* part_b,
                                     void* stream) {
-  US_CHECK_ARG(dy && x && w && part_w && part_b && k >= 1 && k <= kMaxC && c > 0 && c <= 256 && 256 % c == 0,
+  US_CHECK_DTYPE(dtype, "pw_head_bwd");
+  US_CHECK_ARG(k >= 1 && k <= kMaxC && c > 0 && c <= 256 && 256 % c == 0,
                "pw_head_bwd: bad args (k=%d, c=%d must divide 256)", k, c);
-  if (M <= 0) return 0;
+  // element-wise accesses: any ld >= c
+  US_CHECK_ARG(ldx >= c && (!dx || lddx >= c), "pw_head_bwd: ldx (%d) and lddx (%d) must be at least c (%d)", ldx, lddx, c);
+  CHECK_PIXELS(M, hw, "pw_head_bwd");
+  if (M == 0) return 0;
+  US_CHECK_ARG(dy && x && w && part_w && part_b, "pw_head_bwd: null pointer (only dx may be NULL)");
   const int G = unetseg_pw_head_tiles(M);
   const size_t lds = ((size_t)k * c + 256) * sizeof(float);
   DISPATCH_T(dtype, hipLaunchKernelGGL(pw_head_bwd_kernel<T>, dim3(G), dim3(256), lds, (hipStream_t)stream, dy,
@@ -759,6 +799,11 @@ UNETSEG_API int unetseg_pw_head_bwd(int dtype, const float* dy, const void* x, i
 UNETSEG_API int unetseg_attn_apply(int dtype, const void* skip, int lds_, const float* psi, const float* sc,
                                    const float* sh, float* alpha, void* gated, int ldg, long M, int c, void* stream) {
   CHECK_VEC(dtype, c, "attn_apply");
+  CHECK_LD_VEC(dtype, lds_, c, "attn_apply", "lds");
+  CHECK_LD_VEC(dtype, ldg, c, "attn_apply", "ldg");
+  CHECK_PIXELS(M, 1, "attn_apply");
+  if (M == 0) return 0;
+  US_CHECK_ARG(skip && psi && sc && sh && alpha && gated, "attn_apply: null pointer");
   DISPATCH_T(dtype, hipLaunchKernelGGL(attn_apply_kernel<T>, dim3(grid_for(M * c / VE<T>)), dim3(256), 0,
                                        (hipStream_t)stream, (const T*)skip, lds_, psi, sc, sh, alpha, (T*)gated, ldg, M,
                                        c));
@@ -776,6 +821,12 @@ UNETSEG_API int unetseg_attn_bwd1(int dtype, const void* dg, int ldg, const void
   CHECK_VEC(dtype, c, "attn_bwd1");
   const int cv = c / vec_elems(dtype);
   US_CHECK_ARG((cv & (cv - 1)) == 0, "attn_bwd1: C/V must be a power of two");
+  CHECK_LD_VEC(dtype, ldg, c, "attn_bwd1", "ldg");
+  CHECK_LD_VEC(dtype, lds_, c, "attn_bwd1", "lds");
+  CHECK_LD_VEC(dtype, ldds, c, "attn_bwd1", "ldds");
+  CHECK_PIXELS(M, 1, "attn_bwd1");
+  if (M == 0) return 0;
+  US_CHECK_ARG(dg && skip && alpha && psi && mean && inv && dskip && dpsibn && part, "attn_bwd1: null pointer");
   const int G = unetseg_attn_bwd1_tiles(M);
   if (ds_acc)
     DISPATCH_T(dtype, hipLaunchKernelGGL((attn_bwd1_kernel<T, true>), dim3(G), dim3(256), 0, (hipStream_t)stream,
@@ -795,6 +846,11 @@ UNETSEG_API int unetseg_attn_bwd2(int dtype, const float* dpsibn, const float* p
   CHECK_VEC(dtype, c, "attn_bwd2");
   const int cv = c / vec_elems(dtype);
   US_CHECK_ARG(cv <= 256 && 256 % cv == 0, "attn_bwd2: bad C");
+  CHECK_LD_VEC(dtype, ldf, c, "attn_bwd2", "ldf");
+  CHECK_LD_VEC(dtype, lddz, c, "attn_bwd2", "lddz");
+  CHECK_PIXELS(M, 1, "attn_bwd2");
+  if (M == 0) return 0;
+  US_CHECK_ARG(dpsibn && psi && mean && inv && coef && f && wpsi && dzf && part_w && part_b, "attn_bwd2: null pointer");
   const int G = unetseg_pw_small_tiles(M);
   DISPATCH_T(dtype, hipLaunchKernelGGL(attn_bwd2_kernel<T>, dim3(G), dim3(256), 0, (hipStream_t)stream, dpsibn, psi,
                                        mean, inv, coef, (const T*)f, ldf, wpsi, (T*)dzf, lddz, M, c, cv, (int)pw_tile(M), part_w,
