@@ -1,777 +1,22 @@
-// Implicit-GEMM 2-D convolution for NHWC activations on CDNA4 MFMA (gfx950).
+// The conv dispatch: the C ABI of the 2-D convolutions for NHWC activations on gfx950, host code only.
 //
 // Replaces every nn.Conv2d of the reference hot path:
 //   model/resnet_backbone.py:19,33,126,167   model/unet_resnet.py:17,19,72,74,78
 //   model/unet_plain.py:9,12,69              model/unet_attention.py:16,20,24,76
 //   model/unet_multitask.py:17-18,62,64,69
 //
-// Three GEMM views of one conv (x: [N,H,W,Cin] NHWC, y: [N,P,Q,Cout], w: [Cout][Cin][R][S]):
-//   fwd   : Y[m=(n,p,q)][k_out]  = sum_{(r,s,c)} X[n][p*st-pad+r][q*st-pad+s][c] * Wk[k_out][r][s][c]
-//   dgrad : dX[m=(n,h,w)][c]     = sum_{(r,s,k)} dY[n][(h+pad-r)/st][(w+pad-s)/st][k] * Wt[c][r][s][k]
-//           (stride 2: four output-parity classes, each a stride-1 gather over its own tap subset)
-//   wgrad : dW[k_out][(r,s,c)]   = sum_{m=(n,p,q)} dY[m][k_out] * X[n][p*st-pad+r][q*st-pad+s][c]
-// fwd and dgrad are the same "TN" kernel (both operands K-contiguous, gathered with 16-B loads);
-// wgrad has both operands pixel-major and reads MFMA fragments with ds_read_b64_tr_b16.
-//
-// bf16 path: v_mfma_f32_16x16x32_bf16, fp32 accumulate.  fp32 path (parity mode):
-// v_mfma_f32_16x16x4_f32 (exact f32 fma chain).  256 threads = 4 waves in 2x2, one 16x16
-// accumulator per (i,j) subtile; register-staged global->LDS double buffering, one barrier per
-// K step; LDS rows are 128 B (TN) / 256 B (wgrad) with XOR chunk swizzles chosen so that the
-// fragment reads are bank-conflict free.
+// Argument checks, the plan builders that choose a kernel family per call, the host-only queries that
+// report that choice, and calls to the families' launch_* functions: the generic kernels and the
+// split-K reduce (conv_generic.h), the bf16 fast families (conv_fast.h).  No kernel lives here; the
+// three GEMM views of a conv are described in conv_generic.hip, the weight packers are conv_pack.hip.
+// tests/golden/conv_dispatch.json pins the rules of this file entry by entry.
 #include <cstdlib>
 
 #include "common.h"
 #include "conv_fast.h"
+#include "conv_generic.h"
 
 namespace {
-
-constexpr int kBM = 128;  // GEMM M tile of the TN kernel (also the BN-statistics row tile)
-
-// TN kernel LDS image: [row][8 x 16B chunks], chunk swizzle makes ds_read_b128 fragment reads
-// (16 rows x one chunk per 16-lane group) conflict free.
-__device__ __forceinline__ int swz8(int row, int ch) { return ch ^ ((row >> 1) & 7); }
-// wgrad LDS image: [k row][>=16 chunks]; rows {q, 8+q} (q<4) land on distinct chunk pairs so
-// the transposed 4x16 reads of a 32-lane half are conflict free.
-__device__ __forceinline__ int swz_tr(int row) { return ((row & 3) | ((row >> 1) & 4)) << 1; }
-
-struct IgemmArgs {
-  const void* x1;
-  const void* x2;
-  int c1, c2, ldc1, ldc2;  // concat sources (c2 may be 0); channel counts and pixel strides
-  int N, H, W;             // gather-source tensor
-  int hc, wc;              // GEMM-row pixel grid per image
-  int istride;             // source row = hh*istride + dh
-  int r0, rs, nr, dh0, dhs;
-  int s0, ss, ns, dw0, dws;
-  int S;                   // kernel width of the weight image
-  int cin;                 // GEMM K per tap = c1 + c2
-  const void* wt;
-  long ldw;                // weight row length (R*S*cin)
-  int Ng;                  // GEMM N
-  int ostride, ph, pw, OH, OW;  // output pixel = (n, hh*ostride+ph, ww*ostride+pw)
-  void* y;
-  int ldy, accumulate;
-  const float* bias;
-  const float* escale;     // per-output-channel epilogue scale (generic kernel only; may be NULL)
-  const float* in_sc;      // input BN-ReLU prologue (fast register-staged kernels only; may be NULL)
-  const float* in_sh;
-  int relu;
-  float* stats;            // [M tiles][2][Ng] (sum, M2 about the tile mean)
-  int stats_ld;
-  int M;
-};
-
-template <typename T, int BN>
-__global__ __launch_bounds__(256) void igemm_tn_kernel(IgemmArgs a) {
-  constexpr bool kBF = sizeof(T) == 2;
-  constexpr int VE = 16 / sizeof(T);
-  constexpr int BK = 8 * VE;
-  constexpr int BM = kBM;
-  constexpr int A_PER = BM / 32, B_PER = BN / 32;
-  constexpr int FM = BM / 32, FN = BN / 32;
-  __shared__ __attribute__((aligned(16))) uint4 lds[2][(BM + BN) * 8];
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid >> 1, wn = wid & 1;
-  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-  const int kv = tid & 7, rb = tid >> 3;
-  const int hw = a.hc * a.wc;
-
-  int a_nb[A_PER], a_ih[A_PER], a_iw[A_PER];
-  bool a_ok[A_PER];
-#pragma unroll
-  for (int i = 0; i < A_PER; ++i) {
-    int m = m0 + rb + 32 * i;
-    a_ok[i] = m < a.M;
-    int mm = a_ok[i] ? m : 0;
-    int nb = mm / hw, rem = mm - nb * hw;
-    int hh = rem / a.wc, ww = rem - hh * a.wc;
-    a_nb[i] = nb * a.H;
-    a_ih[i] = hh * a.istride;
-    a_iw[i] = ww * a.istride;
-  }
-  const T* x1 = (const T*)a.x1;
-  const T* x2 = (const T*)a.x2;
-  const T* wt = (const T*)a.wt;
-
-  int kc = kv * VE, jr = 0, js = 0;
-  while (kc >= a.cin) {
-    kc -= a.cin;
-    if (++js == a.ns) { js = 0; ++jr; }
-  }
-  const long Ktot = (long)a.nr * a.ns * a.cin;
-  const int nkt = (int)((Ktot + BK - 1) / BK);
-
-  uint4 ra[A_PER], rbv[B_PER];
-  auto gload = [&]() {
-    const bool kok = jr < a.nr;
-    const int r = a.r0 + a.rs * jr, s = a.s0 + a.ss * js;
-    const int dh = a.dh0 + a.dhs * jr, dw = a.dw0 + a.dws * js;
-    const bool first = kc < a.c1;
-#pragma unroll
-    for (int i = 0; i < A_PER; ++i) {
-      int ih = a_ih[i] + dh, iw = a_iw[i] + dw;
-      bool ok = kok && a_ok[i] && ih >= 0 && ih < a.H && iw >= 0 && iw < a.W;
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (ok) {
-        long pix = (long)(a_nb[i] + ih) * a.W + iw;
-        const T* p = first ? x1 + pix * a.ldc1 + kc : x2 + pix * a.ldc2 + (kc - a.c1);
-        v = *reinterpret_cast<const uint4*>(p);
-      }
-      ra[i] = v;
-    }
-    const long wofs = (long)(r * a.S + s) * a.cin + kc;
-#pragma unroll
-    for (int i = 0; i < B_PER; ++i) {
-      int n = n0 + rb + 32 * i;
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (kok && n < a.Ng) v = *reinterpret_cast<const uint4*>(wt + (long)n * a.ldw + wofs);
-      rbv[i] = v;
-    }
-    kc += BK;
-    while (kc >= a.cin) {
-      kc -= a.cin;
-      if (++js == a.ns) { js = 0; ++jr; }
-    }
-  };
-  auto sstore = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < A_PER; ++i) {
-      int row = rb + 32 * i;
-      lds[buf][row * 8 + swz8(row, kv)] = ra[i];
-    }
-#pragma unroll
-    for (int i = 0; i < B_PER; ++i) {
-      int row = rb + 32 * i;
-      lds[buf][(BM + row) * 8 + swz8(row, kv)] = rbv[i];
-    }
-  };
-
-  f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  if (nkt > 0) {
-    gload();
-    sstore(0);
-    __syncthreads();
-  }
-  for (int kt = 0; kt < nkt; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nkt) gload();
-    const uint4* As = &lds[cur][0];
-    const uint4* Bs = &lds[cur][BM * 8];
-    if constexpr (kBF) {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int ch = kk * 4 + (lane >> 4);
-        bf16x8 af[FM], bfr[FN];
-#pragma unroll
-        for (int i = 0; i < FM; ++i) {
-          int row = wm * (BM / 2) + i * 16 + (lane & 15);
-          uint4 v = As[row * 8 + swz8(row, ch)];
-          af[i] = *reinterpret_cast<bf16x8*>(&v);
-        }
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-          int row = wn * (BN / 2) + j * 16 + (lane & 15);
-          uint4 v = Bs[row * 8 + swz8(row, ch)];
-          bfr[j] = *reinterpret_cast<bf16x8*>(&v);
-        }
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-          for (int j = 0; j < FN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-      }
-    } else {
-      const float* Af = reinterpret_cast<const float*>(As);
-      const float* Bf = reinterpret_cast<const float*>(Bs);
-#pragma unroll
-      for (int kk = 0; kk < 8; ++kk) {
-        float af[FM], bfr[FN];
-        const int e = lane >> 4;
-#pragma unroll
-        for (int i = 0; i < FM; ++i) {
-          int row = wm * (BM / 2) + i * 16 + (lane & 15);
-          af[i] = Af[(row * 8 + swz8(row, kk)) * 4 + e];
-        }
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-          int row = wn * (BN / 2) + j * 16 + (lane & 15);
-          bfr[j] = Bf[(row * 8 + swz8(row, kk)) * 4 + e];
-        }
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-          for (int j = 0; j < FN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], bfr[j], acc[i][j], 0, 0, 0);
-      }
-    }
-    if (kt + 1 < nkt) sstore(cur ^ 1);
-    __syncthreads();
-  }
-
-  // ---------------- epilogue ----------------
-  T* y = (T*)a.y;
-  const int ohw = a.hc * a.wc;
-  float colsum[FN], colm2[FN];
-#pragma unroll
-  for (int j = 0; j < FN; ++j) colsum[j] = colm2[j] = 0.f;
-  float vals[FM][FN][4];
-#pragma unroll
-  for (int i = 0; i < FM; ++i) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int m = m0 + wm * (BM / 2) + i * 16 + (lane >> 4) * 4 + e;
-      const bool mok = m < a.M;
-      long opix = 0;
-      if (mok) {
-        int nb = m / ohw, rem = m - nb * ohw;
-        int hh = rem / a.wc, ww = rem - hh * a.wc;
-        opix = ((long)nb * a.OH + hh * a.ostride + a.ph) * a.OW + ww * a.ostride + a.pw;
-      }
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int n = n0 + wn * (BN / 2) + j * 16 + (lane & 15);
-        float v = acc[i][j][e];
-        float vr = 0.f;
-        if (mok && n < a.Ng) {
-          if (a.escale) v = fmaf(v, a.escale[n], a.bias ? a.bias[n] : 0.f);  // == bn_apply's fmaf
-          else if (a.bias) v += a.bias[n];
-          if (a.relu) v = fmaxf(v, 0.f);
-          T* p = y + opix * a.ldy + n;
-          if (a.accumulate) v += (float)(*p);
-          T t = (T)v;
-          *p = t;
-          vr = (float)t;
-          colsum[j] += vr;
-        }
-        vals[i][j][e] = vr;
-      }
-    }
-  }
-  if (a.stats) {  // per-tile column sum and M2 about the tile mean (Chan merge in bn_finalize)
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(&lds[0][0]);  // [0,2BN): sums per (wm, col); [2BN,4BN): M2
-    const int cnt = min(BM, a.M - m0);
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-      float s = colsum[j];
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      if (lane < 16) red[wm * BN + wn * (BN / 2) + j * 16 + lane] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-      const int col = wn * (BN / 2) + j * 16 + (lane & 15);
-      const float mean = (red[col] + red[BN + col]) / (float)cnt;
-      float q = 0.f;
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int m = m0 + wm * (BM / 2) + i * 16 + (lane >> 4) * 4 + e;
-          if (m < a.M) {
-            const float d = vals[i][j][e] - mean;
-            q += d * d;
-          }
-        }
-      q += __shfl_xor(q, 16, 64);
-      q += __shfl_xor(q, 32, 64);
-      colm2[j] = q;
-    }
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-      if (lane < 16) red[2 * BN + wm * BN + wn * (BN / 2) + j * 16 + lane] = colm2[j];
-    __syncthreads();
-    for (int c = tid; c < BN; c += 256) {
-      const int n = n0 + c;
-      if (n < a.Ng) {
-        a.stats[(long)blockIdx.x * 2 * a.Ng + n] = red[c] + red[BN + c];
-        a.stats[(long)blockIdx.x * 2 * a.Ng + a.Ng + n] = red[2 * BN + c] + red[3 * BN + c];
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// wgrad: C[k_out][(r,s,c)] = sum_pix dY[pix][k_out] * im2col(X)[pix][(r,s,c)], split-K over pixels
-// ---------------------------------------------------------------------------------------
-struct WgradArgs {
-  const void* x1;
-  const void* x2;
-  int c1, c2, ldc1, ldc2;
-  int N, H, W, P, Q, stride, pad, R, S;
-  const void* dy;
-  int ldy, Cout;
-  int cin, Ng;
-  long Kpix;
-  int kt_per_split;
-  float* ws;  // [split][Cout][Ng]
-};
-
-template <typename T>
-__global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
-  constexpr bool kBF = sizeof(T) == 2;
-  constexpr int VE = 16 / sizeof(T);
-  constexpr int BM = 128, BN = 128;
-  constexpr int CPR = BM * (int)sizeof(T) / 16;  // 16-B chunks per LDS row
-  constexpr int BKW = kBF ? 32 : 16;             // pixels per K step
-  constexpr int RPP = 256 / CPR;                 // rows per load pass
-  constexpr int PASSES = BKW / RPP;
-  constexpr int FM = 4, FN = 4;
-  __shared__ __attribute__((aligned(16))) uint4 lds[2][2 * BKW * CPR];
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid >> 1, wn = wid & 1;
-  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-  const int cv = tid % CPR, rr = tid / CPR;
-  const long nkt_total = (a.Kpix + BKW - 1) / BKW;
-  const long kt0 = (long)blockIdx.z * a.kt_per_split;
-  const long kt1 = min(nkt_total, kt0 + a.kt_per_split);
-
-  const T* dy = (const T*)a.dy;
-  const int cout = m0 + cv * VE;
-  const bool a_col_ok = cout < a.Cout;
-  const int nn = n0 + cv * VE;
-  const bool b_col_ok = nn < a.Ng;
-  int tap = b_col_ok ? nn / a.cin : 0;
-  int cc = b_col_ok ? nn - tap * a.cin : 0;
-  const int rr_ = tap / a.S, ss_ = tap - rr_ * a.S;
-  const int dh = rr_ - a.pad, dw = ss_ - a.pad;
-  const bool first = cc < a.c1;
-  const T* xb = first ? (const T*)a.x1 + cc : (const T*)a.x2 + (cc - a.c1);
-  const int ldx = first ? a.ldc1 : a.ldc2;
-
-  // pixel state of each of this thread's rows
-  int pn[PASSES], pp[PASSES], pq[PASSES];
-  long pk[PASSES];
-#pragma unroll
-  for (int i = 0; i < PASSES; ++i) {
-    long k = kt0 * BKW + rr + RPP * i;
-    pk[i] = k;
-    long kk = k < a.Kpix ? k : 0;
-    int nb = (int)(kk / ((long)a.P * a.Q));
-    int rem = (int)(kk - (long)nb * a.P * a.Q);
-    pn[i] = nb;
-    pp[i] = rem / a.Q;
-    pq[i] = rem - pp[i] * a.Q;
-  }
-  uint4 ra[PASSES], rbv[PASSES];
-  auto gload = [&]() {
-#pragma unroll
-    for (int i = 0; i < PASSES; ++i) {
-      const bool kok = pk[i] < a.Kpix;
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (kok && a_col_ok) v = *reinterpret_cast<const uint4*>(dy + pk[i] * a.ldy + cout);
-      ra[i] = v;
-      uint4 u = make_uint4(0, 0, 0, 0);
-      const int ih = pp[i] * a.stride + dh, iw = pq[i] * a.stride + dw;
-      if (kok && b_col_ok && ih >= 0 && ih < a.H && iw >= 0 && iw < a.W)
-        u = *reinterpret_cast<const uint4*>(xb + ((long)(pn[i] * a.H + ih) * a.W + iw) * ldx);
-      rbv[i] = u;
-      pk[i] += BKW;
-      pq[i] += BKW;
-      while (pq[i] >= a.Q) {
-        pq[i] -= a.Q;
-        if (++pp[i] >= a.P) { pp[i] = 0; ++pn[i]; }
-      }
-    }
-  };
-  auto sstore = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < PASSES; ++i) {
-      const int row = rr + RPP * i;
-      lds[buf][row * CPR + (cv ^ swz_tr(row))] = ra[i];
-      lds[buf][(BKW + row) * CPR + (cv ^ swz_tr(row))] = rbv[i];
-    }
-  };
-
-  f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nkt = (int)(kt1 - kt0);
-  if (nkt > 0) {
-    gload();
-    sstore(0);
-    __syncthreads();
-  }
-  for (int kt = 0; kt < nkt; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nkt) gload();
-    const uint4* As = &lds[cur][0];
-    const uint4* Bs = &lds[cur][BKW * CPR];
-    if constexpr (kBF) {
-      const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-      bf16x8 af[FM], bfr[FN];
-      auto trfrag = [&](const uint4* base, int col0) -> bf16x8 {
-        const int chunk = (col0 >> 3) + (p >> 1);
-        const int r_a = 8 * g + q, r_b = 8 * g + q + 4;
-        const char* b = reinterpret_cast<const char*>(base);
-        const char* pa = b + r_a * (CPR * 16) + ((chunk ^ swz_tr(r_a)) * 16) + (p & 1) * 8;
-        const char* pb = b + r_b * (CPR * 16) + ((chunk ^ swz_tr(r_b)) * 16) + (p & 1) * 8;
-        s16x4 va = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(pa));
-        s16x4 vb = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(pb));
-        typedef short s16x8 __attribute__((ext_vector_type(8)));
-        s16x8 v = {va[0], va[1], va[2], va[3], vb[0], vb[1], vb[2], vb[3]};
-        return *reinterpret_cast<bf16x8*>(&v);
-      };
-#pragma unroll
-      for (int i = 0; i < FM; ++i) af[i] = trfrag(As, wm * 64 + i * 16);
-#pragma unroll
-      for (int j = 0; j < FN; ++j) bfr[j] = trfrag(Bs, wn * 64 + j * 16);
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    } else {
-      const float* Af = reinterpret_cast<const float*>(As);
-      const float* Bf = reinterpret_cast<const float*>(Bs);
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const int k = kk * 4 + (lane >> 4);
-        float af[FM], bfr[FN];
-#pragma unroll
-        for (int i = 0; i < FM; ++i) {
-          const int m = wm * 64 + i * 16 + (lane & 15);
-          af[i] = Af[k * (CPR * 4) + (((m >> 2) ^ swz_tr(k)) << 2) + (m & 3)];
-        }
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-          const int n = wn * 64 + j * 16 + (lane & 15);
-          bfr[j] = Bf[k * (CPR * 4) + (((n >> 2) ^ swz_tr(k)) << 2) + (n & 3)];
-        }
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-          for (int j = 0; j < FN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], bfr[j], acc[i][j], 0, 0, 0);
-      }
-    }
-    if (kt + 1 < nkt) sstore(cur ^ 1);
-    __syncthreads();
-  }
-  float* ws = a.ws + (long)blockIdx.z * a.Cout * a.Ng;
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + e;
-      if (m >= a.Cout) continue;
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int n = n0 + wn * 64 + j * 16 + (lane & 15);
-        if (n < a.Ng) ws[(long)m * a.Ng + n] = acc[i][j][e];
-      }
-    }
-}
-
-// dW[k][c][tap] (+)= sum_z ws[z][k][tap*cin + c] for c < dw_c.  Block = (output channel k, a run of
-// cw input channels) x SL split lanes: item i = (tap, 4 channels) is one 16-B load per slab; lane l
-// sums slabs l, l+SL, ... in ascending order, the SL partials are combined in LDS in a fixed order
-// (deterministic), and the block's dW run -- cw x taps consecutive floats of PyTorch's [K][C][R][S]
-// -- is written through an LDS transpose, so both the slab reads and the dW writes are contiguous.
-template <int SL>
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* ws, int splits, int Cout, int cin, int taps,
-                                                           float* dw, int dw_c, int accumulate, int cw, int rows_out) {
-  constexpr int IT = 256 / SL;
-  __shared__ float4 red[SL][IT];
-  __shared__ float tile[1024];
-  const long Ng = (long)taps * cin, slab = (long)Cout * Ng;
-  const int nchunk = (dw_c + cw - 1) / cw;
-  const int k = blockIdx.x / nchunk, cc0 = (blockIdx.x - k * nchunk) * cw;
-  if (k >= rows_out) return;  // whole block: a padded output channel, not written
-  const int q4 = cw >> 2, items = taps * q4;
-  const int it = threadIdx.x % IT, sl = threadIdx.x / IT;
-  const int tap = it / q4, cl = (it - tap * q4) * 4;
-  const bool live = it < items && cc0 + cl < dw_c;
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (live) {
-    const float4* p = reinterpret_cast<const float4*>(ws + (long)k * Ng + (long)tap * cin + cc0 + cl);
-    const long s4 = slab >> 2;
-    int z = sl;
-    for (; z + 3 * SL < splits; z += 4 * SL) {
-      const float4 a = p[z * s4], b = p[(z + SL) * s4], c = p[(z + 2 * SL) * s4], d = p[(z + 3 * SL) * s4];
-      v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-      v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
-      v.x += c.x; v.y += c.y; v.z += c.z; v.w += c.w;
-      v.x += d.x; v.y += d.y; v.z += d.z; v.w += d.w;
-    }
-    for (; z < splits; z += SL) {
-      const float4 a = p[z * s4];
-      v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-    }
-  }
-  if constexpr (SL > 1) {
-    red[sl][it] = v;
-    __syncthreads();
-    if (sl == 0)
-      for (int j = 1; j < SL; ++j) {
-        const float4 a = red[j][it];
-        v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-      }
-  }
-  if (sl == 0 && it < items) {  // [c][tap] order of the block's dW run
-    tile[(cl + 0) * taps + tap] = v.x;
-    tile[(cl + 1) * taps + tap] = v.y;
-    tile[(cl + 2) * taps + tap] = v.z;
-    tile[(cl + 3) * taps + tap] = v.w;
-  }
-  __syncthreads();
-  const int run = min(cw, dw_c - cc0) * taps;
-  float* out = dw + ((long)k * dw_c + cc0) * taps;
-  for (int i = threadIdx.x; i < run; i += 256) out[i] = accumulate ? out[i] + tile[i] : tile[i];
-}
-
-// The same sum when there are many slabs (or a 1x1 filter): block = IT consecutive float4 items of a
-// slab x SL split lanes; lane l sums the contiguous slab range [l*R, (l+1)*R), R = ceil(splits/SL),
-// four loads in flight, and the SL partials are added in LDS in lane order (deterministic).  Enough
-// (item, lane) pairs to keep every CU streaming; the dW writes are permuted 4-B stores (float4 for
-// 1x1), a 1/splits share of the traffic.
-template <int SL>
-__global__ __launch_bounds__(256) void wgrad_reduce_split_kernel(const float* ws, int splits, int Cout, int cin,
-                                                                 int taps, float* dw, int dw_c, int accumulate,
-                                                                 int rows_out) {
-  constexpr int IT = 256 / SL;
-  __shared__ float4 red[SL][IT];
-  const long Ng = (long)taps * cin, s4 = (long)Cout * Ng / 4;
-  const int it = threadIdx.x % IT, sl = threadIdx.x / IT;
-  const long q = (long)blockIdx.x * IT + it;
-  const int R = (splits + SL - 1) / SL;
-  const int z1 = min(splits, (sl + 1) * R);
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (q < s4) {
-    const float4* p = reinterpret_cast<const float4*>(ws) + q;
-    int z = sl * R;
-    for (; z + 7 < z1; z += 8) {  // eight slabs in flight, added in slab order
-      float4 a[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) a[u] = p[(z + u) * s4];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        v.x += a[u].x; v.y += a[u].y; v.z += a[u].z; v.w += a[u].w;
-      }
-    }
-    for (; z + 3 < z1; z += 4) {
-      const float4 a = p[z * s4], b = p[(z + 1) * s4], c = p[(z + 2) * s4], d = p[(z + 3) * s4];
-      v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-      v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
-      v.x += c.x; v.y += c.y; v.z += c.z; v.w += c.w;
-      v.x += d.x; v.y += d.y; v.z += d.z; v.w += d.w;
-    }
-    for (; z < z1; ++z) {
-      const float4 a = p[z * s4];
-      v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-    }
-  }
-  if constexpr (SL > 1) {
-    red[sl][it] = v;
-    __syncthreads();
-    if (sl != 0) return;
-    v = red[0][it];
-    for (int j = 1; j < SL; ++j) {
-      const float4 a = red[j][it];
-      v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-    }
-  }
-  if (q >= s4) return;
-  const long k = q * 4 / Ng;
-  if (k >= rows_out) return;  // a padded output channel (after the block's last barrier)
-  const int col = (int)(q * 4 - k * Ng);
-  const int tap = col / cin, c0 = col - tap * cin;
-  if (taps == 1 && c0 + 4 <= dw_c && dw_c % 4 == 0) {
-    float4* o = reinterpret_cast<float4*>(dw + k * dw_c + c0);
-    if (accumulate) {
-      const float4 w = *o;
-      v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
-    }
-    *o = v;
-    return;
-  }
-  const float e4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    if (c0 + e >= dw_c) break;
-    const long dst = (k * dw_c + c0 + e) * taps + tap;
-    dw[dst] = accumulate ? dw[dst] + e4[e] : e4[e];
-  }
-}
-
-// Few slabs of a multi-tap filter: the transposing kernel (coalesced dW runs, one lane group per
-// block); otherwise the split-parallel kernel with ~4 (up to splits / 16) slabs per lane.
-// rows_out (<= cout; -1 = cout): dW rows written -- the rest are the zero-padded output channels of a
-// padded-K GEMM (unetseg_conv2d_wgrad_rows), summed in the slabs but never stored
-static void launch_wgrad_reduce(const float* ws, int splits, int cout, int cin, int taps, float* dw, int dw_c,
-                                int accumulate, hipStream_t st, int rows_out = -1) {
-  if (rows_out < 0 || rows_out > cout) rows_out = cout;
-  if (taps > 1 && splits <= 8 && taps <= 256) {
-    int cw = 4 * (256 / taps);
-    if (cw > 1024 / taps / 4 * 4) cw = 1024 / taps / 4 * 4;  // LDS transpose tile
-    if (cw > 64) cw = 64;
-    if (cw > ceil_div(dw_c, 4) * 4) cw = ceil_div(dw_c, 4) * 4;
-    hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3(cout * ceil_div(dw_c, cw)), dim3(256), 0, st, ws, splits, cout,
-                       cin, taps, dw, dw_c, accumulate, cw, rows_out);
-    return;
-  }
-  int sl = 1;  // at most 16 lanes: 16-item (256-B) runs per slab read, a short LDS combine
-  while (sl < 16 && sl * 4 < splits) sl *= 4;
-  const long s4 = (long)cout * taps * cin / 4;
-  const unsigned blocks = (unsigned)((s4 + 256 / sl - 1) / (256 / sl));
-  switch (sl) {
-    case 16: hipLaunchKernelGGL(wgrad_reduce_split_kernel<16>, dim3(blocks), dim3(256), 0, st, ws, splits, cout, cin, taps, dw, dw_c, accumulate, rows_out); break;
-    case 4: hipLaunchKernelGGL(wgrad_reduce_split_kernel<4>, dim3(blocks), dim3(256), 0, st, ws, splits, cout, cin, taps, dw, dw_c, accumulate, rows_out); break;
-    default: hipLaunchKernelGGL(wgrad_reduce_split_kernel<1>, dim3(blocks), dim3(256), 0, st, ws, splits, cout, cin, taps, dw, dw_c, accumulate, rows_out); break;
-  }
-}
-
-// fp32 [K][C][R][S] -> T [K][R][S][Cpad] (zero-padded channels) and optionally T [C][R][S][K]
-template <typename T>
-__global__ void pack_weights_kernel(const float* w, int K, int C, int R, int S, int Cpad, T* wk, T* wt) {
-  const long total = (long)K * R * S * Cpad;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    long t = i;
-    const int c = (int)(t % Cpad); t /= Cpad;
-    const int s = (int)(t % S); t /= S;
-    const int r = (int)(t % R); t /= R;
-    const int k = (int)t;
-    float v = c < C ? w[(((long)k * C + c) * R + r) * S + s] : 0.f;
-    wk[i] = (T)v;
-    if (wt && c < C) wt[(((long)c * R + r) * S + s) * K + k] = (T)v;
-  }
-}
-
-// Batched pack of many conv weights: one block per (16 output channels x CT input channels) tile of
-// one conv (desc[i].start = its first tile; unetseg_pack_tiles gives a conv's tile count).  The fp32
-// source of a tile is 16 contiguous runs of CT*taps floats ([K][C][R][S] keeps c and the taps of
-// one k together), read with unit-stride coalesced loads into LDS; the wk image ([K][R][S][Cpad])
-// and the transposed wt image ([C][R][S][K]) are then written from LDS, channel-contiguous and
-// k-contiguous respectively.  CT = pow2 in [8, 256] with CT * taps <= 512, so the tile fits the
-// static LDS array; the odd row pitch (513) keeps both LDS read patterns conflict-free.
-constexpr int kPackK = 16;
-
-__host__ __device__ inline int pack_ct(int taps) {
-  int ct = 256;
-  while (ct > 8 && ct * taps > 512) ct >>= 1;
-  return ct;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void pack_weights_batched_kernel(const UnetsegPackDesc* desc, int n) {
-  __shared__ float tile[kPackK][513];
-  const long b = blockIdx.x;
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {  // last desc with start <= b
-    const int mid = (lo + hi + 1) >> 1;
-    if (desc[mid].start <= b) lo = mid; else hi = mid - 1;
-  }
-  const UnetsegPackDesc d = desc[lo];
-  const int taps = d.R * d.S;
-  const int CT = pack_ct(taps);
-  const int lt = (int)(b - d.start);
-  const int ctiles = (d.Cpad + CT - 1) / CT;
-  const int kt = lt / ctiles, ct = lt - kt * ctiles;
-  const int k0 = kt * kPackK, c0 = ct * CT;
-  const int run = CT * taps;                           // floats per k row of the tile
-  const int vrun = max(0, min(CT, d.C - c0)) * taps;   // of which exist in the source
-  const int t = threadIdx.x;
-  if ((d.C * taps) % 4 == 0 && vrun % 4 == 0) {  // 16-B loads (rows start 16-B aligned)
-    // every load of the tile issued before the first LDS store: unconditional (absent rows / columns
-    // read the source's first float4 and are zeroed after); a load under the lane condition was
-    // waited on by itself, one round trip per loop iteration
-    const int run4 = run >> 2;
-    constexpr int NIT = kPackK * 512 / 4 / 256;  // run <= 512
-    float4 v[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = t + it * 256;
-      const int kl = i / run4, j = (i - kl * run4) * 4;
-      const int k = k0 + kl;
-      const bool ok = i < kPackK * run4 && k < d.K && j < vrun;
-      const float4 x = *reinterpret_cast<const float4*>(ok ? d.w + ((long)k * d.C + c0) * taps + j : d.w);
-      v[it] = ok ? x : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = t + it * 256;
-      if (i >= kPackK * run4) break;
-      const int kl = i / run4, j = (i - kl * run4) * 4;
-      tile[kl][j] = v[it].x;
-      tile[kl][j + 1] = v[it].y;
-      tile[kl][j + 2] = v[it].z;
-      tile[kl][j + 3] = v[it].w;
-    }
-  } else {
-    for (int i = t; i < kPackK * run; i += 256) {
-      const int kl = i / run, j = i - kl * run;
-      const int k = k0 + kl;
-      tile[kl][j] = (k < d.K && j < vrun) ? d.w[((long)k * d.C + c0) * taps + j] : 0.f;
-    }
-  }
-  __syncthreads();
-  // wk[k][tap][c], c fastest, 4 channels per store (padding channels c in [C, Cpad) get the zeros
-  // staged above)
-  T* wk = reinterpret_cast<T*>(d.wk);
-  if (d.Cpad % 4 == 0) {
-    const int CT4 = CT >> 2;
-    for (int i = t; i < kPackK * taps * CT4; i += 256) {
-      const int c4 = i % CT4, rest = i / CT4;
-      const int tap = rest % taps, kl = rest / taps;
-      const int k = k0 + kl, c = c0 + c4 * 4;
-      if (k >= d.K || c >= d.Cpad) continue;
-      T o[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (T)tile[kl][(c4 * 4 + e) * taps + tap];
-      T* dst = wk + ((long)k * taps + tap) * d.Cpad + c;
-      if (sizeof(T) == 2) *reinterpret_cast<uint2*>(dst) = *reinterpret_cast<const uint2*>(o);
-      else *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(o);
-    }
-  } else {
-    for (int i = t; i < kPackK * taps * CT; i += 256) {
-      const int cl = i % CT, rest = i / CT;
-      const int tap = rest % taps, kl = rest / taps;
-      const int k = k0 + kl, c = c0 + cl;
-      if (k < d.K && c < d.Cpad) wk[((long)k * taps + tap) * d.Cpad + c] = (T)tile[kl][cl * taps + tap];
-    }
-  }
-  if (d.wt) {  // wt[c][tap][k], k fastest, 8 output channels per store; rows of Kld (>= K) elements
-    T* wt = reinterpret_cast<T*>(d.wt);
-    const int ldk = d.Kld > 0 ? d.Kld : d.K;
-    if (d.K % 8 == 0 && ldk % 8 == 0) {
-      constexpr int K8 = kPackK / 8;
-      for (int i = t; i < K8 * taps * CT; i += 256) {
-        const int k8 = i % K8, rest = i / K8;
-        const int tap = rest % taps, cl = rest / taps;
-        const int k = k0 + k8 * 8, c = c0 + cl;
-        if (k >= d.K || c >= d.C) continue;
-        T o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (T)tile[k8 * 8 + e][cl * taps + tap];
-        T* dst = wt + ((long)c * taps + tap) * ldk + k;
-        if (sizeof(T) == 2) {
-          *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(o);
-        } else {
-          reinterpret_cast<uint4*>(dst)[0] = reinterpret_cast<const uint4*>(o)[0];
-          reinterpret_cast<uint4*>(dst)[1] = reinterpret_cast<const uint4*>(o)[1];
-        }
-      }
-    } else {
-      for (int i = t; i < kPackK * taps * CT; i += 256) {
-        const int kl = i % kPackK, rest = i / kPackK;
-        const int tap = rest % taps, cl = rest / taps;
-        const int k = k0 + kl, c = c0 + cl;
-        if (k < d.K && c < d.C) wt[((long)c * taps + tap) * ldk + k] = (T)tile[kl][cl * taps + tap];
-      }
-    }
-  }
-}
 
 // bf16 fast path (conv_fast.hip) when channels are 64-aligned and every buffer fits 31-bit offsets
 bool fast_tn_args(const IgemmArgs& a, FastTNArgs& f) {
@@ -792,27 +37,6 @@ bool fast_tn_args(const IgemmArgs& a, FastTNArgs& f) {
   f.stats = a.stats; f.stats_ld = a.stats_ld; f.M = a.M;
   f.in_sc = a.in_sc; f.in_sh = a.in_sh;
   return tn_fast_ok(f);
-}
-
-// the generic implicit-GEMM kernel: either dtype, and the only one with the affine epilogue (escale)
-template <typename T>
-int launch_generic_t(const IgemmArgs& a, hipStream_t st) {
-  if (a.M <= 0 || a.Ng <= 0) return 0;
-  US_CHECK_ARG(!a.in_sc, "conv: the BN-ReLU input prologue needs the fast bf16 path");
-  dim3 grid(ceil_div(a.M, kBM), 1, 1);
-  if (a.Ng <= 64) {
-    grid.y = ceil_div(a.Ng, 64);
-    hipLaunchKernelGGL((igemm_tn_kernel<T, 64>), grid, dim3(256), 0, st, a);
-  } else {
-    grid.y = ceil_div(a.Ng, 128);
-    hipLaunchKernelGGL((igemm_tn_kernel<T, 128>), grid, dim3(256), 0, st, a);
-  }
-  US_LAUNCH_CHECK("igemm_tn");
-  return 0;
-}
-
-int launch_generic(int dtype, const IgemmArgs& a, hipStream_t st) {
-  return dtype == DT_BF16 ? launch_generic_t<bf16>(a, st) : launch_generic_t<float>(a, st);
 }
 
 }  // namespace
@@ -1275,21 +499,7 @@ UNETSEG_API int unetseg_conv2d_dgrad_config(int dtype, int ldy, int n, int p, in
 // x = cat([x1, x2]) NHWC [n,h,w,*]; dy NHWC [n,p,q,cout] (pixel stride ldy); dw: fp32
 // [cout][dw_c][r][s] (PyTorch layout; dw_c <= c1+c2 drops zero-padded input channels), written or
 // accumulated.  Every family writes split-K slabs ws[split][cout][r*s*cin] that the deterministic
-// wgrad_reduce_kernel sums into dw; ws: fp32 workspace of unetseg_conv2d_wgrad_workspace() bytes.
-
-// split-K slabs of the generic kernel (K steps of 32 pixels in bf16, 16 in fp32)
-static int wgrad_generic_bk(int dtype) { return dtype == DT_BF16 ? 32 : 16; }
-static int wgrad_generic_splits(int dtype, int Cout, int Ng, long Kpix) {
-  const int bkw = wgrad_generic_bk(dtype);
-  const int tiles = ceil_div(Cout, 128) * ceil_div(Ng, 128);
-  const long nkt = (Kpix + bkw - 1) / bkw;
-  int sp = ceil_div(768, tiles);
-  if (sp < 1) sp = 1;
-  const long max_sp = nkt / 8 > 0 ? nkt / 8 : 1;  // keep >= 8 K steps per split
-  if (sp > max_sp) sp = (int)max_sp;
-  if (sp > 64) sp = 64;
-  return sp;
-}
+// reduce (conv_wgrad_reduce.hip) sums into dw; ws: fp32 workspace of unetseg_conv2d_wgrad_workspace() bytes.
 
 // shape test of the fast bf16 family (conv_fast.hip; split rule: wgrad_fast_splits)
 static bool wgrad_fast_eligible(int dtype, int cin, int cout) {
@@ -1360,8 +570,6 @@ static void plan_wgrad(WgradPlan& pl, int dtype, const void* x1, int c1, int ldc
     a.dy = dy; a.ldy = ldy; a.Cout = cout; a.cin = cin; a.Ng = Ng; a.Kpix = kpix; a.ws = ws;
     pl.kind = kWgGeneric;
     pl.splits = wgrad_generic_splits(dtype, cout, Ng, kpix);
-    const int bkw = wgrad_generic_bk(dtype);
-    a.kt_per_split = (int)(((kpix + bkw - 1) / bkw + pl.splits - 1) / pl.splits);
   }
 }
 
@@ -1376,11 +584,7 @@ static int launch_wgrad(const char* name, int dtype, const WgradPlan& pl, int co
     launch_wgrad_fast(pl.f, pl.splits, st);
     US_LAUNCH_CHECK("wgrad_fast");
   } else {
-    dim3 grid(ceil_div(cout, 128), ceil_div(pl.a.Ng, 128), pl.splits);
-    if (dtype == DT_BF16)
-      hipLaunchKernelGGL(wgrad_kernel<bf16>, grid, dim3(256), 0, st, pl.a);
-    else
-      hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, st, pl.a);
+    launch_wgrad_generic(dtype, pl.a, pl.splits, st);
     US_LAUNCH_CHECK("wgrad");
   }
   launch_wgrad_reduce(ws, pl.splits, cout, cin, taps, dw, dw_c, accumulate, st, dw_rows);
@@ -1453,44 +657,6 @@ UNETSEG_API int unetseg_conv2d_wgrad_config(int dtype, int c1, int ldc1, int c2,
   return pl.kind;
 }
 
-// All of a model's conv weights in one launch.  desc: DEVICE array of n UnetsegPackDesc with
-// ascending `start` = first tile (desc[0].start == 0; a conv has ceil(K/32)*ceil(Cpad/64) tiles);
-// total = number of tiles.
-// blocks of unetseg_pack_conv_weights for one conv (its desc.start advances by this much)
-UNETSEG_API int unetseg_pack_tiles(int K, int Cpad, int taps) {
-  const int ct = pack_ct(taps);
-  return ceil_div(K, kPackK) * ceil_div(Cpad, ct);
-}
-
-UNETSEG_API int unetseg_pack_conv_weights(int dtype, const void* desc, int n, long total, void* stream) {
-  US_CHECK_ARG(desc && n > 0 && total > 0 && total < (1L << 31), "pack_conv_weights: bad args");
-  hipStream_t st = (hipStream_t)stream;
-  const UnetsegPackDesc* d = (const UnetsegPackDesc*)desc;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(pack_weights_batched_kernel<bf16>, dim3(total), dim3(256), 0, st, d, n);
-  else
-    hipLaunchKernelGGL(pack_weights_batched_kernel<float>, dim3(total), dim3(256), 0, st, d, n);
-  US_LAUNCH_CHECK("pack_weights_batched");
-  return 0;
-}
-
-// fp32 [K][C][R][S] -> dtype [K][R][S][Cpad] (+ optional dtype [C][R][S][K] for dgrad)
-UNETSEG_API int unetseg_pack_conv_weight(int dtype, const float* w, int K, int C, int R, int S, int Cpad, void* wk,
-                                         void* wt, void* stream) {
-  US_CHECK_ARG(w && wk && Cpad >= C, "pack_conv_weight: bad args");
-  const long total = (long)K * R * S * Cpad;
-  int blocks = ceil_div(total, 256);
-  if (blocks > 8192) blocks = 8192;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(pack_weights_kernel<bf16>, dim3(blocks), dim3(256), 0, st, w, K, C, R, S, Cpad, (bf16*)wk, (bf16*)wt);
-  else
-    hipLaunchKernelGGL(pack_weights_kernel<float>, dim3(blocks), dim3(256), 0, st, w, K, C, R, S, Cpad, (float*)wk, (float*)wt);
-  US_LAUNCH_CHECK("pack_weights");
-  return 0;
-}
-
-
 // =========================================================================================
 // ResNet stem (model/resnet_backbone.py:126-131: conv 7x7 / stride 2 / pad 3, 3 -> 64, no bias)
 // on the fast implicit-GEMM kernels.  The input is packed width-padded: xp bf16 [N][H][W+8][8]
@@ -1501,25 +667,6 @@ UNETSEG_API int unetseg_pack_conv_weight(int dtype, const float* w, int K, int C
 // wk: bf16 [K][7][64] with wk[k][r][s*8+c] = w[k][c][r][s] (s < 7, c < C), else 0.
 // =========================================================================================
 namespace {
-
-__global__ void stem_pack_weight_kernel(const float* w, int K, int C, bf16* wk) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // over K*7*64
-  if (i >= K * 7 * 64) return;
-  const int k = i / 448, rem = i - k * 448, r = rem / 64, j = rem - r * 64;
-  const int s = j >> 3, c = j & 7;
-  wk[i] = (bf16)((s < 7 && c < C) ? w[((k * C + c) * 7 + r) * 7 + s] : 0.f);
-}
-
-// dw[k][c][r][s] (+)= v[k][s*8 + c][r]   (c < C, s < 7): the split-reduced virtual gradient
-// (wgrad_reduce_kernel, layout [K][64][7]) permuted into PyTorch's [K][C][7][7]
-__global__ void stem_wgrad_remap_kernel(const float* v, int K, int C, float* dw, int accumulate) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // over K*C*49
-  if (i >= K * C * 49) return;
-  const int k = i / (C * 49), rem = i - k * C * 49, c = rem / 49, rs = rem - c * 49;
-  const int r = rs / 7, s = rs - r * 7;
-  const float g = v[((long)k * 64 + s * 8 + c) * 7 + r];
-  dw[i] = accumulate ? dw[i] + g : g;
-}
 
 IgemmArgs stem_args(const void* xp, int n, int h, int w, const void* wk, int K) {
   IgemmArgs a{};
@@ -1546,14 +693,6 @@ FastWgradArgs stem_wgrad_args(const void* xp, int n, int h, int w, const void* d
 }
 
 }  // namespace
-
-UNETSEG_API int unetseg_stem_pack_weight(const float* w, int K, int C, void* wk, void* stream) {
-  US_CHECK_ARG(w && wk && C >= 1 && C <= 8 && K % 8 == 0, "stem_pack_weight: bad args");
-  hipLaunchKernelGGL(stem_pack_weight_kernel, dim3(ceil_div((long)K * 448, 256)), dim3(256), 0, (hipStream_t)stream, w,
-                     K, C, (bf16*)wk);
-  US_LAUNCH_CHECK("stem_pack_weight");
-  return 0;
-}
 
 enum { kStemHalo, kStemFast, kStemNone };
 struct StemPlan {
@@ -1639,8 +778,7 @@ UNETSEG_API int unetseg_stem_wgrad(const void* xp, int n, int h, int w, const vo
   // parallel deterministic split reduce into v = ws tail, [K][64 virtual channels][7 rows], then permute
   float* v = ws + (size_t)splits * K * f.Ng;
   launch_wgrad_reduce(ws, splits, K, 64, 7, v, 64, 0, st);
-  hipLaunchKernelGGL(stem_wgrad_remap_kernel, dim3(ceil_div((long)K * C * 49, 256)), dim3(256), 0, st, v, K, C, dw,
-                     accumulate);
+  launch_stem_wgrad_remap(v, K, C, dw, accumulate, st);
   US_LAUNCH_CHECK("stem_wgrad");
   return 0;
 }

@@ -1,7 +1,7 @@
 // Fast bf16 implicit-GEMM conv kernels for gfx950 (the hot configurations of the U-Net:
-// every conv whose input channels are a multiple of 64).  See conv.hip for the GEMM views.
+// every conv whose input channels are a multiple of 64).  See conv_generic.hip for the GEMM views.
 //
-// What makes them fast relative to the generic kernels in conv.hip:
+// What makes them fast relative to the generic kernels in conv_generic.hip:
 //  * operands are fetched with raw buffer loads (SRD + 32-bit voffset); a padding tap or an
 //    out-of-range row gets an offset past num_records, so the hardware returns zeros: no
 //    branches, no 64-bit address arithmetic in the K loop;
