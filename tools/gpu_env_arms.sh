@@ -1,5 +1,5 @@
 # interleaved bench A/B/C.. of one library build under several environments, $NB rounds:
-#   ARMS="base=;serial512=UNETSEG_WG_SERIAL_HW=262144" BENCH_ARGS="--model attention_unet --batch 8"
+#   ARMS="base=;noserial=UNETSEG_WG_SERIAL_LAYERS=" BENCH_ARGS="--model attention_unet --batch 8"
 # (arm = name=ENV [ENV ...]; an empty ENV runs the defaults)
 set -o pipefail
 cd $GRAFT_REPO_ROOT

@@ -179,10 +179,6 @@ OVERLAP = os.environ.get("UNETSEG_NO_OVERLAP", "0") != "1"
 _SIDE = {}
 
 
-#: priority of the weight-gradient stream (torch convention: lower = higher priority)
-SIDE_PRIORITY = int(os.environ.get("UNETSEG_SIDE_PRIORITY", "0"))
-
-
 #: UNETSEG_SIDE_CUMASK=<hex word>: the weight-gradient stream runs only on the CUs of that 32-bit
 #: pattern, repeated over the chip (e.g. 55555555: every other CU), so its persistent kernels, which
 #: hold a CU's LDS for their whole life, never keep a compute-stream kernel off every CU
@@ -201,7 +197,7 @@ def side_stream(device):
                 lib.stream_create_cumask(ctypes.addressof(words), n, ctypes.addressof(out))
             _SIDE[key] = torch.cuda.ExternalStream(out.value, device=device)
         else:
-            _SIDE[key] = torch.cuda.Stream(device, priority=SIDE_PRIORITY)
+            _SIDE[key] = torch.cuda.Stream(device)
     return _SIDE[key]
 
 
@@ -232,7 +228,7 @@ class Ctx:
         self.grad_hook = None  # called with a param after its gradient is final (DDP bucketing)
         self.finish_hook = None  # called once the tape is done, before the compute stream joins the side
         self.side = None  # weight-gradient stream, set while backward runs with OVERLAP
-        self.deferred = []  # weight-gradient launches held back until a flush point (defer_wgrad)
+        self.deferred = []  # weight-gradient launches held back until a flush point (_wgrad_place)
         self.flushed = False  # the flush marker has run in this backward
         self.has_marker = False  # the forward recorded a flush marker (models without one defer nothing)
         self.layer = None  # the encoder layer the forward is in (flush_point), for WG_SERIAL_LAYERS
@@ -291,46 +287,31 @@ class Ctx:
                     self.grad_hook(p, stream)
 
 
-#: weight gradients of 3x3 convs whose output has >= this many pixels per image are held back in
-#: backward until a flush marker (flush_point): they then run on the side stream beside the encoder's
-#: memory-bound layers instead of beside the data gradients of their own layers.  Default: the
-#: decoder's virtual-concat convs (MFMA-bound, each used to share the CUs with its own equally heavy data
-#: gradient), released when the backward reaches layer4 -- step A/B +0.45 % (three interleaved repeats);
-#: holding back every decoder 3x3 wgrad, or releasing at layer3, measured neutral to -3 %
-#: (0 = off; UNETSEG_WG_DEFER_HW, UNETSEG_WG_DEFER_CAT, UNETSEG_WG_FLUSH)
+#: Where a conv's weight gradient runs (_wgrad_place): by default on the side stream, beside the layer's own data
+#: gradient.  The decoder's virtual-concat 3x3 convs with >= WG_DEFER_HW output pixels per image are held back
+#: until the flush marker (flush_point) and run beside the encoder's memory-bound layers (UNETSEG_WG_DEFER_HW,
+#: 0 = off); WG_FLUSH places the marker in forward order: "decoder" (before the decoder) or "layer4" / "layer3" /
+#: "layer2" (before that encoder layer; UNETSEG_WG_FLUSH).  The encoder layers in WG_SERIAL_LAYERS ("stem",
+#: "layer1", ...) run theirs on the compute stream, as the side stream lags it at the end of the backward
+#: (UNETSEG_WG_SERIAL_LAYERS, comma list).  The measurements behind these defaults and the arms that lost (every
+#: 3x3 held back, large maps serial, enqueued after the data gradient, a stream priority): DESIGN.md, rounds 4-6.
 WG_DEFER_HW = int(os.environ.get("UNETSEG_WG_DEFER_HW", "1024"))
-#: where the flush marker sits in forward order: "decoder" (before the decoder), "layer4" / "layer3" / "layer2"
-#: (before that encoder layer: in backward the held-back gradients start once that layer's backward is done)
-#: (round 5, replayed step plan: layer3 +0.1-0.3 % over layer4; round 4's eager host had layer4 best)
 WG_FLUSH = os.environ.get("UNETSEG_WG_FLUSH", "layer3")
-
-
-#: weight gradients of 3x3 convs whose output has >= this many pixels per image run on the compute stream
-#: right after their data gradient instead of beside it on the side stream (0 = never): two persistent
-#: one-block-per-CU halo kernels sharing the CUs each take ~2x their isolated time (UNETSEG_WG_SERIAL_HW)
-WG_SERIAL_HW = int(os.environ.get("UNETSEG_WG_SERIAL_HW", "0"))
-#: encoder layers ("stem", "layer1", ...) whose weight gradients run on the compute stream: at the end of
-#: the backward the weight-gradient stream lags the compute stream (UNETSEG_WG_SERIAL_LAYERS, comma list).
-#: Round 4 (eager host) measured stem + layer1 best; with the step plan's replayed host (round 5, two
-#: interleaved repeats each) the stem alone: C2 1007-1011 vs 997-998 img/s, C5 807-810 vs 797-799
-#: (layer1 serial no better than stem + layer1; none equal to stem within noise)
 WG_SERIAL_LAYERS = frozenset(v for v in os.environ.get("UNETSEG_WG_SERIAL_LAYERS", "stem").split(",") if v)
-
-#: the side-stream weight gradient is enqueued after its layer's data gradient and waits for it
-#: (UNETSEG_WG_AFTER_DGRAD=1): the data gradient -- the critical path -- then gets the CUs first instead
-#: of both becoming ready on the same event and sharing them (round 6 experiment)
-WG_AFTER_DGRAD = os.environ.get("UNETSEG_WG_AFTER_DGRAD", "0") == "1"
-
-#: only the virtual-concat convs (the decoder's unetUp conv1) are held back (UNETSEG_WG_DEFER_CAT=0: every 3x3)
-WG_DEFER_CAT = os.environ.get("UNETSEG_WG_DEFER_CAT", "1") == "1"
+WG_SIDE, WG_SERIAL, WG_DEFERRED = "side", "serial", "deferred"
 
 
-def defer_wgrad(ctx, N, Pq, Qq, R, S, x2):
-    """hold this conv's weight gradient until the flush marker (never after it has run: the
-    encoder's own gradients are not pushed to the end of the backward)"""
-    return (bool(WG_DEFER_HW) and ctx.side is not None and ctx.has_marker and not ctx.flushed
-            and Pq * Qq >= WG_DEFER_HW and R * S > 1
-            and (x2 is not None or not WG_DEFER_CAT))
+def _wgrad_place(ctx, layer, Pq, Qq, R, S, concat):
+    """one weight gradient's placement, decided in its backward.  WG_SIDE: launched now, before the data gradient,
+    on the side stream (the compute stream without overlap: _wgrad_stream); WG_SERIAL: on the compute stream after
+    the data gradient; WG_DEFERRED: held until the flush marker (never once it has run: the encoder's own gradients
+    are not pushed to the end of the backward).  layer: ctx.layer at forward time; concat: a virtual-concat conv.
+    Two quirks are behaviour: ctx.layer is None until the first flush_point, so a stem that runs through conv()
+    (fp32, or UNETSEG_NO_FAST_STEM=1) is never serial; stem_conv passes "stem" and is serial iff the set has it."""
+    if (WG_DEFER_HW and ctx.side is not None and ctx.has_marker and not ctx.flushed and
+            Pq * Qq >= WG_DEFER_HW and R * S > 1 and concat):
+        return WG_DEFERRED
+    return WG_SERIAL if layer in WG_SERIAL_LAYERS else WG_SIDE
 
 
 def flush_point(ctx, where):
@@ -390,11 +371,15 @@ class PackedConv:
 
     def padk(self, dt):
         """the one place that decides whether this conv's gradients run through a 64-padded dY (conv()
-        reads it for out.kpad; the padded data gradient needs wt rows Kld wide): narrow bf16 1x1
+        reads kpad() for out.kpad; the padded data gradient needs wt rows Kld wide): narrow bf16 1x1
         stride-1 convs.  conv() also requires a single input (no virtual concat)."""
         K = self.K
         return (PAD_K and dt == DT_BF16 and self.R == 1 and self.S == 1 and K % 64 != 0 and K % 8 == 0 and
                 self.conv.stride in (1, (1, 1)))
+
+    def kpad(self, dt):
+        """Kp, the 64-rounded width of that padded dY (and of the wt rows); 0 when not padded"""
+        return -(-self.K // 64) * 64 if self.padk(dt) else 0
 
     def ensure(self, ctx, need_t):
         """allocate the packed images for ctx's dtype/device (no launch)"""
@@ -403,7 +388,7 @@ class PackedConv:
             self.wk = ctx.empty(K, R, S, self.cpad)
             self.wt = None
             self.dt = ctx.dt
-            self.kld = -(-K // 64) * 64 if self.padk(ctx.dt) else K
+            self.kld = self.kpad(ctx.dt) or K
         if need_t and self.wt is None:
             # [Cpad][R][S][Kld]: the padded input channels' rows (and padded K columns) stay zero (the pack
             # writes C rows x K columns), so a data gradient over all Cpad channels is well defined
@@ -459,9 +444,7 @@ class PackTable:
 # ------------------------------------------------------------------------------------------------
 def pack_input(ctx, x, cpad=8):
     """NCHW fp32 image batch -> NHWC node with channels zero-padded to cpad"""
-    x = x.contiguous()
-    if x.dtype != torch.float32:
-        x = x.float()
+    x = x.contiguous().float()
     N, C, H, W = x.shape
     y = ctx.empty(N, H, W, cpad)
     lib.pack_input(ctx.dt, P(x), N, C, H, W, cpad, P(y), ctx.stream)
@@ -515,6 +498,56 @@ def _wgrad_stream(ctx, ws_bytes, reads, serial=False):
     return side, workspace(ws_bytes, ctx.device, 1), side.cuda_stream
 
 
+def _q_fwd_mask(dt, ldx, N, H, W, ldy):
+    # a launching entry point as a shape query: zeros for x | wk, bias, y | mask bits, stream.  1: has the kernel
+    return _q("conv2d_fwd_mask", dt, 0, ldx, N, H, W, 0, 0, 0, ldy, 0, 0)
+
+
+def _q_dgrad_post(dt, ldy, N, Pq, Qq, K, C, R, S, stride, pad, H, W, kind, ldaux):
+    # zeros: dY | wt | dX (pixel stride C) | aux | sc, sh, mean, inv, partials, rows, stream.  Rows of partials, or <= 0
+    return _q("conv2d_dgrad_post", dt, 0, ldy, N, Pq, Qq, 0, K, C, R, S, stride, pad, 0, C, H, W, kind, 0, ldaux,
+              0, 0, 0, 0, 0, 0, 0)
+
+
+def _q_dgrad_post_res(dt, ldy, N, Pq, Qq, K, C, ldg, ldy3):
+    # zeros: dY | wt | g | y3 | mean, inv, mask bits, y2, ldy2, mean2, inv2, partials, rows, stream.  Rows, or <= 0
+    return _q("conv2d_dgrad_post_res", dt, 0, ldy, N, Pq, Qq, 0, K, C, 0, ldg, 0, ldy3, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+
+
+def _halo64_bias_relu(pc, C1, x2, relu, st):
+    """single input, 64 -> 64, 3x3 / stride 1 / pad 1, bias, ReLU, no BN statistics: the halo kernel's epilogues"""
+    return (x2 is None and relu and pc.conv.bias is not None and st is None and pc.K == 64 and C1 == 64 and
+            (pc.R, pc.S, pc.conv.stride, pc.conv.padding) == (3, 3, 1, 1))
+
+
+FWD_PLAIN, FWD_BNRELU_IN, FWD_HEAD, FWD_MASK = "fwd", "fwd_bnrelu_in", "fwd_head", "fwd_mask"
+
+
+def _fwd_variant(ctx, pc, X1, y, lazy, x2, relu, st, head):
+    """the forward entry point conv() runs: unetseg_conv2d_fwd, or where the library has the shape _bnrelu_in (a
+    lazy input), _head (the 1x1 head in the epilogue) or _mask (the ReLU mask as bits for the consumer's dgrad)"""
+    if lazy is not None:
+        return FWD_BNRELU_IN
+    N, H, W, C1 = X1.shape
+    if not _halo64_bias_relu(pc, C1, x2, relu, st):
+        return FWD_PLAIN
+    if (head is not None and FUSE_HEAD and head.bias is not None and
+            _q("conv2d_fwd_head_ok", ctx.dt, ldp(X1), N, H, W, ldp(y), head.weight.shape[0])):
+        return FWD_HEAD
+    mask = RELU_BITS and FUSE and ctx.training and ctx.tape is not None
+    return FWD_MASK if mask and _q_fwd_mask(ctx.dt, ldp(X1), N, H, W, ldp(y)) == 1 else FWD_PLAIN
+
+
+def _padded_dy(ctx, out, dY, K, Kp):
+    """dY in Kp zero-padded channels (1x1 convs with a narrow output, PackedConv.padk).  The consumer's backward
+    wrote dY into the zeroed padded buffer (out.kpad, gbuf); a gradient adopted from elsewhere is copied into one"""
+    if out.gpad is not None and dY is out.grad:
+        return out.gpad
+    dYp = torch.zeros(*dY.shape[:-1], Kp, dtype=ctx.tdtype, device=ctx.device)
+    lib.add(ctx.dt, P(dY), ldp(dY), P(dYp), Kp, dYp.numel() // Kp, K, ctx.stream)
+    return dYp
+
+
 def conv(ctx, x1, pc, x2=None, relu=False, stats=False, out=None, head=None):
     """y = conv(cat[x1, x2]) (+bias if the conv has one, ReLU).  Stride/padding come from the
     Conv2d container.  out: an NHWC view (pixel stride >= K) to write y into, e.g. a channel slice
@@ -523,11 +556,9 @@ def conv(ctx, x1, pc, x2=None, relu=False, stats=False, out=None, head=None):
     (unetseg_conv2d_fwd_head) and ride on the returned node for pw_head.  Returns (Node y, BN
     partials or None)."""
     stride, pad = pc.conv.stride, pc.conv.padding
-    lazy = x1.lazy
-    if lazy is not None and not (x2 is None and ctx.dt == DT_BF16 and pc.R == 1 and pc.S == 1 and stride == 1 and
-                                 pad == 0 and x1.data.shape[-1] % 64 == 0 and pc.K % 64 == 0):
+    if x1.lazy is not None and not _applies_bn_on_load(ctx, pc, x1, x2):
         _materialize(ctx, x1)
-        lazy = None
+    lazy = x1.lazy
     use(x1, x2)
     # x1's first consumer in the forward delivers the last contribution to its gradient in the backward
     last_grad = x1.uses == 1
@@ -543,40 +574,33 @@ def conv(ctx, x1, pc, x2=None, relu=False, stats=False, out=None, head=None):
         tile = _q("conv2d_fwd_tile_m", ctx.dt, C1, ldp(X1), C2, ldp(X2), N, H, W, K, R, S, stride, pad)
         st = (ctx.f32(math.ceil(M / tile), 2, K), tile)  # [row tiles][sum, M2][K]
     b = pc.conv.bias
-    mbits = None
-    if lazy is not None:
+    mbits = logits = None
+    variant = _fwd_variant(ctx, pc, X1, y, lazy, x2, relu, st, head)
+    if variant == FWD_BNRELU_IN:
         with _probe("igemm_tn", flops, 1, ("fwd_bnrelu_in",) + desc):
             lib.conv2d_fwd_bnrelu_in(ctx.dt, P(X1), C1, ldp(X1), N, H, W, P(pc.wk), K, P(lazy.sc), P(lazy.sh), P(b),
                                      int(relu), P(y), ldp(y), P(st[0] if st else None), ctx.stream)
-    elif head is not None and (FUSE_HEAD and x2 is None and relu and st is None and b is not None and
-                               head.bias is not None and K == 64 and
-                               C1 == 64 and (R, S, stride, pad) == (3, 3, 1, 1) and
-                               _q("conv2d_fwd_head_ok", ctx.dt, ldp(X1), N, H, W, ldp(y), head.weight.shape[0])):
+    elif variant == FWD_HEAD:
         Kh = head.weight.shape[0]
         logits = torch.empty((N, Kh, Pq, Qq), dtype=torch.float32, device=ctx.device)
         with _probe("igemm_tn", flops, 1, ("fwd",) + desc):
             lib.conv2d_fwd_head(ctx.dt, P(X1), ldp(X1), N, H, W, P(pc.wk), P(b), P(y), ldp(y), Kh, P(head.weight),
                                 P(head.bias), P(logits), ctx.stream)
-        head = (head, logits)
+    elif variant == FWD_MASK:
+        mbits = torch.empty(M * 8, dtype=torch.uint8, device=ctx.device)
+        with _probe("igemm_tn", flops, 1, ("fwd",) + desc):
+            rc = lib.conv2d_fwd_mask(ctx.dt, P(X1), ldp(X1), N, H, W, P(pc.wk), P(b), P(y), ldp(y), P(mbits),
+                                     ctx.stream)
+        if rc != 0:
+            raise RuntimeError(f"unetseg_conv2d_fwd_mask failed ({rc}): {last_error()}")
     else:
-        head = None
-        if (RELU_BITS and FUSE and relu and b is not None and x2 is None and st is None and ctx.training and
-                ctx.tape is not None and K == 64 and C1 == 64 and (R, S, stride, pad) == (3, 3, 1, 1) and
-                _q("conv2d_fwd_mask", ctx.dt, 0, ldp(X1), N, H, W, 0, 0, 0, ldp(y), 0, 0) == 1):
-            mbits = torch.empty(M * 8, dtype=torch.uint8, device=ctx.device)
-            with _probe("igemm_tn", flops, 1, ("fwd",) + desc):
-                rc = lib.conv2d_fwd_mask(ctx.dt, P(X1), ldp(X1), N, H, W, P(pc.wk), P(b), P(y), ldp(y), P(mbits),
-                                         ctx.stream)
-            if rc != 0:
-                raise RuntimeError(f"unetseg_conv2d_fwd_mask failed ({rc}): {last_error()}")
-        else:
-            with _probe("igemm_tn", flops, 1, ("fwd",) + desc):
-                lib.conv2d_fwd(ctx.dt, P(X1), C1, ldp(X1), P(X2), C2, ldp(X2), N, H, W, P(pc.wk), K, R, S, stride,
-                               pad, P(b), int(relu), P(y), ldp(y), P(st[0] if st else None), ctx.stream)
+        with _probe("igemm_tn", flops, 1, ("fwd",) + desc):
+            lib.conv2d_fwd(ctx.dt, P(X1), C1, ldp(X1), P(X2), C2, ldp(X2), N, H, W, P(pc.wk), K, R, S, stride,
+                           pad, P(b), int(relu), P(y), ldp(y), P(st[0] if st else None), ctx.stream)
     out = Node(y)
-    out.head = head
-    if x2 is None and pc.padk(ctx.dt):
-        out.kpad = -(-K // 64) * 64
+    out.head = (head, logits) if variant == FWD_HEAD else None
+    if x2 is None:
+        out.kpad = pc.kpad(ctx.dt)
     if relu:
         out.fuse = Producer(POST_RELU, y, mbits=mbits)
     _tap(ctx, "conv", out, [x1, x2], conv=pc.conv, relu=relu)
@@ -601,20 +625,10 @@ def conv(ctx, x1, pc, x2=None, relu=False, stats=False, out=None, head=None):
         else:
             assert b is None, "conv with bias and no ReLU is not on the hot path"
             dY = dA
-        # 1x1 convs with a narrow output (the attention gates' theta/phi, K = inter = 32): both
-        # gradient GEMMs reduce over or produce K, below the fast tiles' 64-channel granule, so dY
-        # is zero-padded to Kp channels and the padded rows of dW / columns of W^T are zero.  The
-        # consumer's backward wrote dY into the zeroed padded buffer (out.kpad, gbuf); a gradient
-        # adopted from elsewhere is copied into one
-        Kp = K
-        if out.kpad:
-            Kp = out.kpad
-            if out.gpad is not None and dY is out.grad:
-                dY = out.gpad
-            else:
-                dYp = torch.zeros(N, Pq, Qq, Kp, dtype=ctx.tdtype, device=ctx.device)
-                lib.add(ctx.dt, P(dY), ldp(dY), P(dYp), Kp, M, K, ctx.stream)
-                dY = dYp
+        Kp = out.kpad or K  # both gradients of a padded-K conv run over Kp channels (_padded_dy)
+        if Kp != K:
+            assert (R, S, stride, pad) == (1, 1, 1, 0)
+            dY = _padded_dy(ctx, out, dY, K, Kp)
         cin = C1 + C2
 
         def launch_wgrad(serial=False):
@@ -623,67 +637,51 @@ def conv(ctx, x1, pc, x2=None, relu=False, stats=False, out=None, head=None):
             ws_bytes = _q("conv2d_wgrad_workspace", ctx.dt, N, Pq, Qq, Kp, cin, R, S)
             reads = (dY, X1, X2) + ((lazy.sc, lazy.sh) if lazy is not None else ())
             side, ws, wst = _wgrad_stream(ctx, ws_bytes, reads, serial)
-            if Kp != K:
-                # the Kp-row GEMM (dY's padded columns are zero) reduced straight into the K-row gradient
-                with _probe("wgrad", flops, 1, ("wgrad_padk",) + desc, stream=side):
+            label = "wgrad_padk" if Kp != K else "wgrad_bnrelu_in" if lazy is not None else "wgrad"
+            with _probe("wgrad", flops, 1, (label,) + desc, stream=side):
+                if Kp != K:  # the Kp-row GEMM (dY's padded columns are zero) reduced straight into the K-row gradient
                     lib.conv2d_wgrad_rows(ctx.dt, P(X1), C1, ldp(X1), N, H, W, P(dY), Kp, Kp, 1, 1, 1, 0, P(ws),
                                           ws.numel(), P(pc.conv.weight.grad), pc.C, 1, K, wst)
-            elif lazy is not None:
-                with _probe("wgrad", flops, 1, ("wgrad_bnrelu_in",) + desc, stream=side):
+                elif lazy is not None:
                     lib.conv2d_wgrad_bnrelu_in(ctx.dt, P(X1), C1, ldp(X1), N, H, W, P(dY), ldp(dY), K, P(lazy.sc),
                                                P(lazy.sh), P(ws), ws.numel(), P(pc.conv.weight.grad), pc.C, 1, wst)
-            else:
-                with _probe("wgrad", flops, 1, ("wgrad",) + desc, stream=side):
+                else:
                     lib.conv2d_wgrad(ctx.dt, P(X1), C1, ldp(X1), P(X2), C2, ldp(X2), N, H, W, P(dY), ldp(dY), K, R, S,
                                      stride, pad, P(ws), ws.numel(), P(pc.conv.weight.grad), pc.C, 1, wst)
             return side
 
-        deferred = defer_wgrad(ctx, N, Pq, Qq, R, S, x2)
-        serial = not deferred and ((bool(WG_SERIAL_HW) and Pq * Qq >= WG_SERIAL_HW and R * S > 1) or
-                                   layer in WG_SERIAL_LAYERS)
-        wstream = None
-        after = WG_AFTER_DGRAD and not deferred and not serial
-        if not deferred and not serial and not after:
-            wstream = launch_wgrad()
+        def dgrad(g, acc, cin_, label):
+            """dX = g[..., :cin_] (+)= the data gradient of the Kp-channel dY through the Kp-wide rows of pc.wt"""
+            launches = _dgrad_launches(ctx, ldp(dY), N, Pq, Qq, Kp, cin_, R, S, stride, pad, H, W)
+            with _probe("igemm_tn", flops, launches, (label,) + desc):
+                lib.conv2d_dgrad(ctx.dt, P(dY), ldp(dY), N, Pq, Qq, P(pc.wt), Kp, cin_, R, S, stride, pad, P(g),
+                                 ldp(g), H, W, acc, ctx.stream)
+
+        place = _wgrad_place(ctx, layer, Pq, Qq, R, S, x2 is not None)
+        wstream = launch_wgrad() if place == WG_SIDE else None
         # data gradient (reads the packed weight pc.wt: the parameter is reported done after it)
-        if Kp != K:
-            if x1.need_grad:
-                assert pc.kld == Kp, "the padded-K data gradient reads the Kp-wide packed wt (PackedConv.kld)"
-                g, acc = gbuf(ctx, x1)
-                with _probe("igemm_tn", flops, 1, ("dgrad_padk",) + desc):
-                    lib.conv2d_dgrad(ctx.dt, P(dY), Kp, N, Pq, Qq, P(pc.wt), Kp, C1, 1, 1, 1, 0, P(g), ldp(g), H, W,
-                                     acc, ctx.stream)
-        elif x2 is None:
-            assert pc.wt is None or pc.kld == K, "a plain data gradient reads K-wide wt rows (PackedConv.kld)"
-            if x1.need_grad and not _dgrad_fused(ctx, x1, dY, pc, N, H, W, C1, Pq, Qq, flops, desc, last_grad):
-                g, acc = gbuf(ctx, x1)
-                with _probe("igemm_tn", flops, _dgrad_launches(ctx, ldp(dY), N, Pq, Qq, K, C1, R, S, stride, pad, H, W),
-                            ("dgrad",) + desc):
-                    lib.conv2d_dgrad(ctx.dt, P(dY), ldp(dY), N, Pq, Qq, P(pc.wt), K, C1, R, S, stride, pad, P(g),
-                                     ldp(g), H, W, acc, ctx.stream)
-        elif x1.need_grad or x2.need_grad:
-            assert pc.wt is None or pc.kld == K, "a concat data gradient reads K-wide wt rows (PackedConv.kld)"
-            g = ctx.empty(N, H, W, cin)
-            with _probe("igemm_tn", flops, _dgrad_launches(ctx, ldp(dY), N, Pq, Qq, K, cin, R, S, stride, pad, H, W),
-                        ("dgrad",) + desc):
-                lib.conv2d_dgrad(ctx.dt, P(dY), ldp(dY), N, Pq, Qq, P(pc.wt), K, cin, R, S, stride, pad, P(g), cin,
-                                 H, W, 0, ctx.stream)
-            give_grad(ctx, x1, g[..., :C1])
-            give_grad(ctx, x2, g[..., C1:])
-        if after:
-            wstream = launch_wgrad()  # the side stream waits for the data gradient just enqueued
-        if serial:
-            launch_wgrad(serial=True)  # after the data gradient, on the compute stream
-        if deferred:
-            def late():
-                ctx.param_done(pc.conv.weight, stream=launch_wgrad())
-                ctx.param_done(b)
-            ctx.deferred.append(late)
-        else:
-            # the side stream's last launch is still this wgrad (only the data gradient, on the compute
-            # stream, was enqueued since)
-            ctx.param_done(pc.conv.weight, stream=wstream)
+        assert pc.kld == Kp or (Kp == K and pc.wt is None), "the data gradient reads Kp-wide wt rows (PackedConv.kld)"
+        if x2 is not None:
+            if x1.need_grad or x2.need_grad:
+                g = ctx.empty(N, H, W, cin)
+                dgrad(g, 0, cin, "dgrad")
+                give_grad(ctx, x1, g[..., :C1])
+                give_grad(ctx, x2, g[..., C1:])
+        elif x1.need_grad and (Kp != K or
+                               not _dgrad_fused(ctx, x1, dY, pc, N, H, W, C1, Pq, Qq, flops, desc, last_grad)):
+            dgrad(*gbuf(ctx, x1), C1, "dgrad_padk" if Kp != K else "dgrad")
+
+        def finish():
+            # SIDE: the side stream's last launch is still this wgrad (only the data gradient, on the compute
+            # stream, was enqueued since).  SERIAL launches here, on the compute stream after the data gradient
+            ws = wstream if place == WG_SIDE else launch_wgrad(serial=place == WG_SERIAL)
+            ctx.param_done(pc.conv.weight, stream=ws)
             ctx.param_done(b)
+
+        if place == WG_DEFERRED:
+            ctx.deferred.append(finish)
+        else:
+            finish()
 
     ctx.push(bwd)
     return out, st
@@ -744,8 +742,7 @@ def _dgrad_fused_res(ctx, x1, dY, pc, N, H, W, C1, Pq, Qq, flops, desc, last_gra
     y3, s1, y2, s2 = p.act, p.st, p.act2, p.st2
     K = pc.K
     g = x1.grad
-    rows = _q("conv2d_dgrad_post_res", ctx.dt, 0, ldp(dY), N, Pq, Qq, 0, K, C1, 0, ldp(g), 0, ldp(y3),
-              0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+    rows = _q_dgrad_post_res(ctx.dt, ldp(dY), N, Pq, Qq, K, C1, ldp(g), ldp(y3))
     if rows <= 0:
         return False
     nq = 3 if y2 is not None else 2
@@ -783,15 +780,15 @@ def _dgrad_fused(ctx, x1, dY, pc, N, H, W, C1, Pq, Qq, flops, desc, last_grad=Fa
     stride, pad = pc.conv.stride, pc.conv.padding
     args = [ctx.dt, P(dY), ldp(dY), N, Pq, Qq, P(pc.wt), K, C1, R, S, stride, pad]
     coeffs = [P(st.sc), P(st.sh), P(st.mean), P(st.inv)] if kind == POST_BN_RELU else [0, 0, 0, 0]
-    qargs = (ctx.dt, 0, ldp(dY), N, Pq, Qq, 0, K, C1, R, S, stride, pad, 0, C1, H, W)
+    qargs = (ctx.dt, ldp(dY), N, Pq, Qq, K, C1, R, S, stride, pad, H, W)
     rows = -1
     if kind == POST_RELU and p.mbits is not None:
         # the producer stored its ReLU mask as bits: post 4 reads them instead of the activation
-        rows = _q("conv2d_dgrad_post", *qargs, POST_RELU_BITS, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+        rows = _q_dgrad_post(*qargs, POST_RELU_BITS, 0)
         if rows > 0:
             kind, aux = POST_RELU_BITS, p.mbits
     if rows <= 0:
-        rows = _q("conv2d_dgrad_post", *qargs, kind, 0, ldp(aux), 0, 0, 0, 0, 0, 0, 0)
+        rows = _q_dgrad_post(*qargs, kind, ldp(aux))
     if rows <= 0:
         return False
     g = ctx.empty(N, H, W, C1)
@@ -816,9 +813,7 @@ def stem_conv(ctx, x, conv_mod):
     image batch, bf16 only: the input is packed width-padded so one filter row's 8 taps x 8 channels
     are 128 contiguous bytes, and the conv runs as a K = 7 x 64 implicit GEMM on the fast kernels
     (unetseg_stem_fwd / unetseg_stem_wgrad).  Returns (Node y, BN partial stats) like conv()."""
-    x = x.contiguous()
-    if x.dtype != torch.float32:
-        x = x.float()
+    x = x.contiguous().float()
     N, C, H, W = x.shape
     K = conv_mod.weight.shape[0]
     xp = ctx.empty(N, H, W + 8, 8)
@@ -842,7 +837,9 @@ def stem_conv(ctx, x, conv_mod):
         if dY is None:
             return
         ws_bytes = lib.stem_wgrad_workspace(N, H, W, K)
-        side, ws, wst = _wgrad_stream(ctx, ws_bytes, (dY, xp), serial="stem" in WG_SERIAL_LAYERS)
+        # no data gradient (the image needs none) and never a concat: side or serial only
+        serial = _wgrad_place(ctx, "stem", Pq, Qq, 7, 7, False) == WG_SERIAL
+        side, ws, wst = _wgrad_stream(ctx, ws_bytes, (dY, xp), serial=serial)
         with _probe("wgrad", flops, 1, ("stem_wgrad",) + desc, stream=side):
             lib.stem_wgrad(P(xp), N, H, W, P(dY), ldp(dY), K, P(ws), ws.numel(), P(conv_mod.weight.grad), C, 1, wst)
         ctx.param_done(conv_mod.weight, stream=side)
@@ -874,24 +871,31 @@ def _merge_rows(ctx, part, C, G, nq, M=0, tile=0):
     return out, G2, tile * 16
 
 
-def _bn_coeffs(ctx, bn, st, M, tile=None):
-    """st: (partials [G][2][C], row tile) from conv(), or a bare partials tensor with `tile` given"""
+def _bn_params(bnm):
+    """a BatchNorm2d's tensors and scalars as _bn_coeffs takes them"""
+    return bnm.weight, bnm.bias, bnm.running_mean, bnm.running_var, bnm.num_batches_tracked, bnm.momentum, bnm.eps
+
+
+def _bn_coeffs(ctx, weight, bias, rmean, rvar, nbt, momentum, eps, st, M, tile=None, merge=True):
+    """the BNState of one call; training also updates rmean / rvar / nbt (num_batches_tracked).  st: (partials
+    [G][2][C], row tile) from conv(), or a bare partials tensor with `tile` given (unused in eval mode);
+    merge: large row counts go through _merge_rows first"""
     if isinstance(st, tuple):
         st, tile = st
-    C = bn.weight.shape[0]
+    C = weight.shape[0]
     s = BNState()
     if ctx.training:
         # one allocation for the four coefficient vectors (the host cost of a step is per allocation)
         s.sc, s.sh, s.mean, s.inv = ctx.f32(4, C).unbind(0)
-        st, G, tile = _merge_rows(ctx, st, C, st.shape[0], 2, M, tile)
-        lib.bn_finalize(P(st), C, G, M, tile, P(bn.weight), P(bn.bias), P(bn.running_mean), P(bn.running_var),
-                        P(bn.num_batches_tracked), bn.momentum, bn.eps, P(s.mean), P(s.inv), P(s.sc), P(s.sh),
-                        ctx.stream)
+        G = st.shape[0]
+        if merge:
+            st, G, tile = _merge_rows(ctx, st, C, G, 2, M, tile)
+        lib.bn_finalize(P(st), C, G, M, tile, P(weight), P(bias), P(rmean), P(rvar), P(nbt), momentum, eps, P(s.mean),
+                        P(s.inv), P(s.sc), P(s.sh), ctx.stream)
     else:
         s.sc, s.sh = ctx.f32(2, C).unbind(0)
         s.mean = s.inv = None
-        lib.bn_eval_coeffs(C, P(bn.weight), P(bn.bias), P(bn.running_mean), P(bn.running_var), bn.eps, P(s.sc),
-                           P(s.sh), ctx.stream)
+        lib.bn_eval_coeffs(C, P(weight), P(bias), P(rmean), P(rvar), eps, P(s.sc), P(s.sh), ctx.stream)
     return s
 
 
@@ -900,6 +904,13 @@ MASK_BITS = os.environ.get("UNETSEG_NO_MASK_BITS", "0") != "1"
 
 #: BN-ReLU applied by the consuming 1x1 conv on load instead of a separate pass (UNETSEG_NO_BN_PROLOGUE=1: off)
 BN_PROLOGUE = os.environ.get("UNETSEG_NO_BN_PROLOGUE", "0") != "1"
+
+
+def _applies_bn_on_load(ctx, pc, x1, x2):
+    """conv pc can apply lazy x1's BN-ReLU on load (unetseg_conv2d_fwd_bnrelu_in / _wgrad_bnrelu_in): a bf16
+    single-input 1x1 / stride 1 / pad 0 conv between 64-multiple channel counts"""
+    return (x2 is None and ctx.dt == DT_BF16 and (pc.R, pc.S, pc.conv.stride, pc.conv.padding) == (1, 1, 1, 0) and
+            x1.data.shape[-1] % 64 == 0 and pc.K % 64 == 0)
 
 
 def _materialize(ctx, node):
@@ -945,13 +956,13 @@ def bn(ctx, y, st, bnm, relu=True, res=None, res_bn=None, lazy=False):
     Y = y.data
     N, H, W, C = Y.shape
     M = N * H * W
-    s1 = _bn_coeffs(ctx, bnm, st, M)
+    s1 = _bn_coeffs(ctx, *_bn_params(bnm), st, M)
     mode, R, s2 = 0, None, None
     if res is not None:
         mode, R = 1, res.data
     elif res_bn is not None:
         mode, R = 2, res_bn[0].data
-        s2 = _bn_coeffs(ctx, res_bn[2], res_bn[1], M)
+        s2 = _bn_coeffs(ctx, *_bn_params(res_bn[2]), res_bn[1], M)
     mbits = None
     if lazy and BN_PROLOGUE and relu and mode == 0 and ctx.training and ctx.dt == DT_BF16:
         out = Node(Y)
@@ -1049,6 +1060,17 @@ def pool_out(h, k, s, ceil_mode):
     return o
 
 
+def _push_input_grad(ctx, out, x, launch, fused=None):
+    """the backward of a single-input op out = f(x): x.grad (+)= launch(gout, g, accumulate), skipped when out got
+    no gradient or x wants none.  fused(gout): tried first, an attempt that delivers x's whole gradient itself;
+    True when it ran"""
+    def bwd():
+        if out.grad is not None and x.need_grad and not (fused is not None and fused(out.grad)):
+            launch(out.grad, *gbuf(ctx, x))
+
+    ctx.push(bwd)
+
+
 def maxpool(ctx, x, k, s, ceil_mode):
     use(x)
     X = x.data
@@ -1060,14 +1082,8 @@ def maxpool(ctx, x, k, s, ceil_mode):
     out = Node(y)
     _tap(ctx, "maxpool", out, [x], k=k, s=s, ceil_mode=ceil_mode)
 
-    def bwd():
-        if out.grad is None or not x.need_grad:
-            return
-        g, acc = gbuf(ctx, x)
-        lib.maxpool_bwd(ctx.dt, P(out.grad), ldp(out.grad), P(idx), N, H, W, C, k, s, Pq, Qq, P(g), ldp(g), acc,
-                        ctx.stream)
-
-    ctx.push(bwd)
+    _push_input_grad(ctx, out, x, lambda gout, g, acc: lib.maxpool_bwd(
+        ctx.dt, P(gout), ldp(gout), P(idx), N, H, W, C, k, s, Pq, Qq, P(g), ldp(g), acc, ctx.stream))
     return out
 
 
@@ -1080,12 +1096,9 @@ def upsample2x(ctx, x, align_corners):
     out = Node(y)
     _tap(ctx, "resize", out, [x], size=(2 * H, 2 * W), align_corners=bool(align_corners))
 
-    def bwd():
-        if out.grad is None or not x.need_grad:
-            return
-        _upsample_bwd(ctx, x, out.grad, align_corners)
-
-    ctx.push(bwd)
+    _push_input_grad(ctx, out, x, lambda gout, g, acc: lib.upsample2x_bwd(
+        ctx.dt, P(gout), ldp(gout), N, H, W, C, int(align_corners), P(g), ldp(g), acc, ctx.stream),
+        fused=lambda gout: _upsample_bwd(ctx, x, gout, align_corners))
     return out
 
 
@@ -1109,22 +1122,21 @@ def _head_may_fuse(ctx, x, X):
 
 
 def _upsample_bwd(ctx, x, gout, align_corners):
-    """x.grad (+)= the backward of y = upsample2x(x) for the gradient gout of y"""
+    """the fused backward of y = upsample2x(x) for the gradient gout of y, when x is a ReLU output consumed
+    only here (unetUp conv2 -> next block's upsample): x.grad = the upsample's backward under that ReLU's
+    mask, and the producer conv's bias-gradient partials ride along.  False (nothing done) otherwise"""
     X = x.data
     N, H, W, C = X.shape
-    if _upsample_may_fuse(ctx, x, X):
-        # x is a ReLU output consumed only here (unetUp conv2 -> next block's upsample): its
-        # backward mask and the producer conv's bias-gradient partials ride along
-        rows = _q("upsample2x_bwd_tiles", ctx.dt, N, H, W, C)
-        g = ctx.empty(N, H, W, C)
-        part = ctx.f32(rows, 2, C)
-        lib.upsample2x_bwd_relu(ctx.dt, P(gout), ldp(gout), N, H, W, C, int(align_corners), P(X), ldp(X), P(g),
-                                ldp(g), P(part), rows, ctx.stream)
-        x.grad = g
-        x.fused = Partials(part, rows)
-        return
-    g, acc = gbuf(ctx, x)
-    lib.upsample2x_bwd(ctx.dt, P(gout), ldp(gout), N, H, W, C, int(align_corners), P(g), ldp(g), acc, ctx.stream)
+    if not _upsample_may_fuse(ctx, x, X):
+        return False
+    rows = _q("upsample2x_bwd_tiles", ctx.dt, N, H, W, C)
+    g = ctx.empty(N, H, W, C)
+    part = ctx.f32(rows, 2, C)
+    lib.upsample2x_bwd_relu(ctx.dt, P(gout), ldp(gout), N, H, W, C, int(align_corners), P(X), ldp(X), P(g),
+                            ldp(g), P(part), rows, ctx.stream)
+    x.grad = g
+    x.fused = Partials(part, rows)
+    return True
 
 
 def resize_bilinear(ctx, x, oh, ow, align_corners):
@@ -1138,14 +1150,8 @@ def resize_bilinear(ctx, x, oh, ow, align_corners):
     out = Node(y)
     _tap(ctx, "resize", out, [x], size=(oh, ow), align_corners=bool(align_corners))
 
-    def bwd():
-        if out.grad is None or not x.need_grad:
-            return
-        g, acc = gbuf(ctx, x)
-        lib.resize_bilinear_bwd(ctx.dt, P(out.grad), ldp(out.grad), N, H, W, C, oh, ow, int(align_corners), P(g),
-                                ldp(g), acc, ctx.stream)
-
-    ctx.push(bwd)
+    _push_input_grad(ctx, out, x, lambda gout, g, acc: lib.resize_bilinear_bwd(
+        ctx.dt, P(gout), ldp(gout), N, H, W, C, oh, ow, int(align_corners), P(g), ldp(g), acc, ctx.stream))
     return out
 
 
@@ -1159,14 +1165,8 @@ def pad2d(ctx, x, top, left, oh, ow):
     out = Node(y)
     _tap(ctx, "pad", out, [x], top=top, left=left, size=(oh, ow))
 
-    def bwd():
-        if out.grad is None or not x.need_grad:
-            return
-        g, acc = gbuf(ctx, x)
-        lib.pad2d_bwd(ctx.dt, P(out.grad), ldp(out.grad), N, H, W, C, top, left, oh, ow, P(g), ldp(g), acc,
-                      ctx.stream)
-
-    ctx.push(bwd)
+    _push_input_grad(ctx, out, x, lambda gout, g, acc: lib.pad2d_bwd(
+        ctx.dt, P(gout), ldp(gout), N, H, W, C, top, left, oh, ow, P(g), ldp(g), acc, ctx.stream))
     return out
 
 
@@ -1253,7 +1253,7 @@ def attention_gate(ctx, skip, gate, gm, pth, pph):
     pst = ctx.f32(G, 2, 1)
     lib.pw_small_fwd(ctx.dt, P(F_), ldp(F_), M, M, Ci, 1, P(psi_conv.weight), P(psi_conv.bias), P(psi),
                      P(pst) if ctx.training else 0, ctx.stream)
-    s = _bn_coeffs(ctx, psi_bn, pst, M, lib.pw_small_tile(M))
+    s = _bn_coeffs(ctx, *_bn_params(psi_bn), pst, M, lib.pw_small_tile(M))
     S_ = skip.data
     Cs = S_.shape[-1]
     alpha = ctx.f32(M)
@@ -1383,22 +1383,16 @@ def bn_relu_prefix(ctx, block, width, bnm, idx=None):
             t = torch.zeros(C, dtype=torch.float32, device=dev)
             return t.index_copy_(0, idx, v.detach())
         g, b, rm, rv = phys(bnm.weight), phys(bnm.bias), phys(bnm.running_mean), phys(bnm.running_var)
-    s = BNState()
-    s.sc, s.sh = ctx.f32(C), ctx.f32(C)
+    part = None
     if ctx.training:
-        G = lib.channel_stats_tiles(M, STATS_TILE)
-        part = ctx.f32(G, 2, C)
+        part = ctx.f32(lib.channel_stats_tiles(M, STATS_TILE), 2, C)
         lib.channel_stats(ctx.dt, P(Y), ldp(Y), M, C, STATS_TILE, P(part), ctx.stream)
-        s.mean, s.inv = ctx.f32(C), ctx.f32(C)
-        lib.bn_finalize(P(part), C, G, M, STATS_TILE, P(g), P(b), P(rm), P(rv), P(bnm.num_batches_tracked),
-                        bnm.momentum, bnm.eps, P(s.mean), P(s.inv), P(s.sc), P(s.sh), ctx.stream)
-        if idx is not None:
-            with torch.no_grad():
-                bnm.running_mean.copy_(rm.index_select(0, idx))
-                bnm.running_var.copy_(rv.index_select(0, idx))
-    else:
-        s.mean = s.inv = None
-        lib.bn_eval_coeffs(C, P(g), P(b), P(rm), P(rv), bnm.eps, P(s.sc), P(s.sh), ctx.stream)
+    # these partials are finalized as they are at every size (merge=False: no _merge_rows pass)
+    s = _bn_coeffs(ctx, g, b, rm, rv, bnm.num_batches_tracked, bnm.momentum, bnm.eps, part, M, STATS_TILE, merge=False)
+    if ctx.training and idx is not None:
+        with torch.no_grad():
+            bnm.running_mean.copy_(rm.index_select(0, idx))
+            bnm.running_var.copy_(rv.index_select(0, idx))
     a = ctx.empty(N, H, W, C)
     lib.bn_apply(ctx.dt, P(Y), ldp(Y), P(s.sc), P(s.sh), 0, 0, 0, 0, 0, 1, P(a), C, M, C, ctx.stream)
     out = Node(a)
@@ -1409,7 +1403,7 @@ def bn_relu_prefix(ctx, block, width, bnm, idx=None):
             return
         if not ctx.training:
             raise NotImplementedError("backward through eval-mode BatchNorm is not on the hot path")
-        Gr = lib.reduce_tiles(ctx.dt, M, C, None, None)
+        Gr = _q("reduce_tiles", ctx.dt, M, C, None, None)
         part = ctx.f32(3, C, Gr)
         _bn_bwd_reduce(ctx, dA, Y, s, M, C, part, Gr, remask=True)
         coef = ctx.f32(6, C)
