@@ -532,6 +532,27 @@ int unetseg_boundary_counts(const int32_t* pred, const int32_t* target, const ui
                             const int32_t* dP, const int32_t* dG, int N, int H, int W, int c, int ignore, int K,
                             int biou_d2, int64_t* counts, void* stream);
 
+/* ---- boundary (distance-map) loss (Kervadec et al., MIDL 2019; no reference counterpart) -------------
+ * out planar fp32 [B][nch][H][W] (nch 2: z = o1 - o0, nch 1: z = o0), tgt int64 [B][H][W], class c,
+ * ignore_index (-1: none).  Per image fg = {t == c}, bg = {t != c, t != ignore_index}; d2fg / d2bg the
+ * exact squared distance to the nearest fg / bg pixel of the image (unetseg_edt_sqdist over both site maps of
+ * the batch in one call).  phi = +sqrt(d2fg) on bg, -(sqrt(d2bg) - 1) on fg, 0 on ignored pixels and wherever
+ * the distance it would use is UNETSEG_EDT_INF (so an image without fg, or without bg, contributes 0).
+ * With p = sigmoid(z) and Nvalid the non-ignored pixels of the batch:
+ *   loss[0] = inv_norm / Nvalid * sum_valid p phi          (0 when Nvalid == 0; never weighted)
+ *   gz [B][H][W] (may be NULL) = weight * p (1 - p) phi inv_norm / Nvalid on valid pixels, 0 on ignored ones;
+ *   added to gz when accumulate != 0, so the term lands on a region loss's gz (unetseg_dz_to_dout then spreads
+ *   the sum).  phi [B][H][W] (may be NULL) receives the signed distance map.
+ * Nvalid is counted on the device while the site maps are written and 1 / Nvalid enters gz as it is written:
+ * no host wait and no second pass.  loss, gz and phi are bitwise reproducible.  Checked before any launch:
+ * null out / tgt / ws / loss, nch in {1, 2}, B, H, W > 0, H, W <= 16384, ignore_index != c, ws_bytes, and a
+ * 16-byte aligned ws.  Nothing past the B * H * W elements of gz and phi and past ws_bytes is written. */
+size_t unetseg_boundary_loss_workspace(int B, int H, int W); /* host only */
+int unetseg_boundary_loss_fwd(const float* out, int nch, const int64_t* tgt, int B, int H, int W, int c,
+                              long ignore_index /* -1: none */, float inv_norm, float weight, void* ws,
+                              size_t ws_bytes, float* gz, int accumulate, float* phi /* may be NULL */, float* loss,
+                              void* stream);
+
 /* ---- device augmentation of the loader (utils/hf_dataloader.py:67-105, 111-180, 183-213) -------
  * Replaces HFUnetDataset.get_random_data + preprocess + hf_unet_dataset_collate for one batch:
  * PIL BICUBIC image / NEAREST mask resize (bit-exact), flip, paste on the grey / zero canvas,

@@ -42,14 +42,13 @@
 // once with the number of its lanes that hit it, and the block adds its non-zero bins to `counts` when it
 // is done.  LDS holds kBins bins (both histograms at K = 4096); a larger K runs one grid row per window of
 // kBins bins, each over all pixels, counting the bins of its window only.
+#include "boundary_edt.h"
 #include "elem_util.h"
 
 namespace {
 
 constexpr int kSeg = 64;            // rows per column segment = width of a row chunk
 constexpr unsigned kNone = 32768u;  // "no site" as a 16-bit column distance; kNone^2 == kEdtInf
-constexpr int kEdtInf = 1 << 30;    // UNETSEG_EDT_INF
-constexpr int kEdtMax = 16384;      // largest H and W
 constexpr int kBins = 2 * (4096 + 2);  // histogram bins a block holds in LDS (32.8 KB)
 constexpr int kMaxK = 65536;
 
@@ -288,6 +287,22 @@ int boundary_geometry(const char* name, int N, int H, int W, long& total) {
 
 }  // namespace
 
+// the launches of the distance transform (boundary_edt.h); arguments checked by the caller
+void launch_edt_sqdist(const uint8_t* sites, int N, int H, int W, int32_t* d2, hipStream_t st) {
+  unsigned* out = (unsigned*)d2;
+  const int nseg = (H + kSeg - 1) / kSeg;
+  const long cols = (long)N * nseg * W;
+  hipLaunchKernelGGL(edt_col_local_kernel, dim3(grid_for(cols)), dim3(256), 0, st, sites, H, W, nseg, cols,
+                     nseg == 1 ? 1 : 0, out);
+  if (nseg > 1)
+    hipLaunchKernelGGL(edt_col_merge_kernel, dim3(grid_for(cols)), dim3(256), 0, st, H, W, nseg, cols, out);
+  const int chunks = (W + kSeg - 1) / kSeg;
+  const long rows = (long)N * H;
+  const size_t lds = (size_t)(chunks * kSeg + chunks) * sizeof(unsigned short);  // <= 33 KB
+  hipLaunchKernelGGL(edt_row_kernel, dim3((unsigned)(rows < (1L << 20) ? rows : (1L << 20))), dim3(256), lds, st, W,
+                     chunks, rows, out);
+}
+
 // the segment of the column pass and the chunk of the row pass (host only): seams lie at its multiples
 UNETSEG_API int unetseg_edt_chunk(int* len) {
   US_CHECK_ARG(len, "edt_chunk: null pointer");
@@ -313,19 +328,7 @@ UNETSEG_API int unetseg_edt_sqdist(const uint8_t* sites, int N, int H, int W, in
   US_CHECK_ARG(sites && d2, "edt_sqdist: null pointer");
   long total;
   if (boundary_geometry("edt_sqdist", N, H, W, total)) return 1;
-  hipStream_t st = (hipStream_t)stream;
-  unsigned* out = (unsigned*)d2;
-  const int nseg = (H + kSeg - 1) / kSeg;
-  const long cols = (long)N * nseg * W;
-  hipLaunchKernelGGL(edt_col_local_kernel, dim3(grid_for(cols)), dim3(256), 0, st, sites, H, W, nseg, cols,
-                     nseg == 1 ? 1 : 0, out);
-  if (nseg > 1)
-    hipLaunchKernelGGL(edt_col_merge_kernel, dim3(grid_for(cols)), dim3(256), 0, st, H, W, nseg, cols, out);
-  const int chunks = (W + kSeg - 1) / kSeg;
-  const long rows = (long)N * H;
-  const size_t lds = (size_t)(chunks * kSeg + chunks) * sizeof(unsigned short);  // <= 33 KB
-  hipLaunchKernelGGL(edt_row_kernel, dim3((unsigned)(rows < (1L << 20) ? rows : (1L << 20))), dim3(256), lds, st, W,
-                     chunks, rows, out);
+  launch_edt_sqdist(sites, N, H, W, d2, (hipStream_t)stream);
   US_LAUNCH_CHECK("edt_sqdist");
   return 0;
 }

@@ -61,12 +61,16 @@ class MultiTaskUNet(HipModel):
 
 class MultiTaskLoss(nn.Module):
     """unet_multitask.py:109-139: total = seg_loss(seg.squeeze(1), y.float()) + w * CE(cls, c).
-    seg_loss_fn None / nn.BCEWithLogitsLoss -> fused BCE kernel; lovasz_hinge_loss -> Lovasz kernel."""
+    seg_loss_fn None / nn.BCEWithLogitsLoss -> fused BCE kernel; lovasz_hinge_loss -> Lovasz kernel.
+    boundary_weight > 0 adds that multiple of losses.boundary_loss of the seg logits to the seg term (no
+    reference counterpart; constant over a run)."""
 
-    def __init__(self, seg_loss_fn=None, cls_loss_weight=1.0):
+    def __init__(self, seg_loss_fn=None, cls_loss_weight=1.0, boundary_weight=0.0, boundary_normalize=True):
         super().__init__()
         self.seg_loss_fn = seg_loss_fn or nn.BCEWithLogitsLoss()
         self.cls_loss_weight = cls_loss_weight
+        self.boundary_weight = boundary_weight
+        self.boundary_normalize = boundary_normalize
 
     def forward(self, seg_logits, cls_logits, seg_targets, cls_targets):
         fn = self.seg_loss_fn
@@ -78,4 +82,5 @@ class MultiTaskLoss(nn.Module):
             kind = "lovasz_hinge"
         else:
             raise NotImplementedError(f"unsupported seg loss {fn}")
-        return losses.multitask_loss(seg_logits, cls_logits, seg_targets, cls_targets, self.cls_loss_weight, kind)
+        return losses.multitask_loss(seg_logits, cls_logits, seg_targets, cls_targets, self.cls_loss_weight, kind,
+                                     self.boundary_weight, self.boundary_normalize)

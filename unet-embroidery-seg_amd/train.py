@@ -169,10 +169,12 @@ def train(args):
         else:
             pos_weight = torch.tensor([float(args.pos_weight)], dtype=torch.float32, device=device)
 
+    # the boundary-loss term of the binary and multitask objectives (training and the reported losses alike)
+    bnd = dict(boundary_weight=args.boundary_loss_weight, boundary_normalize=not args.boundary_loss_pixels)
     criterion = None
     if args.task == "multitask":
         seg_fn = lovasz_hinge_loss if args.loss == "lovasz_hinge" else torch.nn.BCEWithLogitsLoss()
-        criterion = MultiTaskLoss(seg_loss_fn=seg_fn, cls_loss_weight=args.cls_loss_weight)
+        criterion = MultiTaskLoss(seg_loss_fn=seg_fn, cls_loss_weight=args.cls_loss_weight, **bnd)
 
     mtb = args.max_train_batches or None
     mvb = args.max_val_batches or None
@@ -194,7 +196,7 @@ def train(args):
             loss = train_one_epoch_binary(model, optimizer, train_loader, device, loss_name=args.loss,
                                           pos_weight=pos_weight, gpu_used=torch.cuda.memory_allocated() / 2**20,
                                           scaler=scaler if args.amp else None, epoch=epoch, train_epoch=args.epochs,
-                                          ignore_index=None, max_batches=mtb)
+                                          ignore_index=None, max_batches=mtb, **bnd)
         else:  # train.py:285-294
             loss = train_one_epoch(model, optimizer, train_loader, device, args.use_dice, args.loss == "focal",
                                    torch.cuda.memory_allocated() / 2**20, num_classes,
@@ -211,7 +213,7 @@ def train(args):
             score = float(metrics["IoU"])
         elif args.task == "binary":
             metrics = evaluate_binary(model, val_loader, device, loss_name=args.loss, pos_weight=pos_weight,
-                                      ignore_index=None, max_batches=mvb)
+                                      ignore_index=None, max_batches=mvb, **bnd)
             score = float(metrics["IoU"])
         else:
             metrics = evaluate(model, val_loader, device, args.use_dice, args.loss == "focal", num_classes,
@@ -246,7 +248,7 @@ def train(args):
                 test_metrics = evaluate(model, test_loader, device, True, False, num_classes)
             else:
                 test_metrics = evaluate_binary(model, test_loader, device, loss_name=args.loss, pos_weight=pos_weight,
-                                               ignore_index=None, max_batches=mtest)
+                                               ignore_index=None, max_batches=mtest, **bnd)
             with open(os.path.join(exp_folder, "test_metrics.json"), "w", encoding="utf-8") as f:
                 json.dump(test_metrics, f, ensure_ascii=False, indent=2)
             # fixed-sample visual export of the test split (train.py:476-486; HF datasets only)
@@ -286,6 +288,11 @@ def parse_args(argv=None):
     p.add_argument("--cls-loss-weight", default=1.0, type=float)
     p.add_argument("--loss", default="lovasz_hinge", choices=["bce", "lovasz_hinge", "ce", "focal", "lovasz_softmax"],
                    help="lovasz_softmax: the multiclass task's IoU surrogate (--task multiclass only)")
+    p.add_argument("--boundary-loss-weight", default=0.0, type=float,
+                   help="adds this multiple of the boundary (distance-map) loss to the region loss (--task binary and "
+                        "multitask; constant over the run)")
+    p.add_argument("--boundary-loss-pixels", action="store_true",
+                   help="boundary loss in pixel units instead of fractions of the image diagonal")
     p.add_argument("--pos-weight", default="auto")
     p.add_argument("--pos-weight-samples", default=80, type=int)
     p.add_argument("--use-dice", action=argparse.BooleanOptionalAction, default=True)
@@ -311,6 +318,10 @@ def parse_args(argv=None):
     p.add_argument("--synthetic-val", default=16, type=int, help="synthetic val/test images")
     p.add_argument("--out-dir", default="logs")
     args = p.parse_args(argv)
+    if args.boundary_loss_weight < 0:
+        p.error("--boundary-loss-weight must be >= 0")
+    if args.task == "multiclass" and (args.boundary_loss_weight > 0 or args.boundary_loss_pixels):
+        p.error("--boundary-loss-weight / --boundary-loss-pixels apply to --task binary and multitask only")
     if args.pos_weight == "":
         args.pos_weight = None
     return args

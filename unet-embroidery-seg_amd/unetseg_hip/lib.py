@@ -142,6 +142,8 @@ SIGNATURES = {
     "unetseg_edt_sqdist": (I, [P, I, I, I, P, P]),
     "unetseg_edt_chunk": (I, [P]),
     "unetseg_boundary_counts": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, P, P]),
+    "unetseg_boundary_loss_workspace": (SZ, [I, I, I]),
+    "unetseg_boundary_loss_fwd": (I, [P, I, P, I, I, I, I, L, F, F, P, SZ, P, I, P, P, P]),
 }
 
 #: functions returning a value rather than a status (no RuntimeError on non-zero)

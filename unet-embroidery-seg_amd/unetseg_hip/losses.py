@@ -7,13 +7,18 @@ logit difference (utils/train_and_eval.py:106-113) fused into the kernel:
 multitask_loss: seg BCE/Lovasz + w * CE over the cls head (model/unet_multitask.py:119-139).
 Multiclass task: ce_loss / focal_loss / dice_loss (one fused kernel pair) and lovasz_softmax_loss (the
 multiclass form of the Lovasz hinge, on the same segmented radix sort).
+boundary_loss / signed_distance: the distance-map loss of Kervadec et al. (MIDL 2019) on the exact GPU distance
+transform; boundary_weight= of binary_segmentation_loss and multitask_loss adds it to the region loss.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
+from . import plan as _plan
 from .lib import lib
-from .ops import P, workspace
+from .ops import P, _q, workspace
 
 
 def _stream(dev):
@@ -130,15 +135,123 @@ def _seg_forward(kind, out, nch, tgt, B, Pn, pos_weight, need_grad, ignore_index
     return loss, gz
 
 
+def _inv_norm(H, W, normalize):
+    """the boundary term's unit: 1 / the image diagonal (the term then lies in [-1, 1] whatever the input
+    size), or 1 for the paper's pixel units"""
+    return 1.0 / math.sqrt(H * H + W * W) if normalize else 1.0
+
+
+def _boundary_forward(out, nch, tgt, H, W, c, ignore_index, normalize, weight, gz, accumulate, phi=None):
+    """unetseg_boundary_loss_fwd on prepared tensors -> the unweighted loss (device scalar); gz (may be
+    None) gets, or with `accumulate` is added, weight * dL/dz"""
+    dev = out.device
+    B = out.shape[0]
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    ws = workspace(_q("boundary_loss_workspace", B, H, W), dev)
+    lib.boundary_loss_fwd(P(out), nch, P(tgt), B, H, W, int(c), -1 if ignore_index is None else int(ignore_index),
+                          _inv_norm(H, W, normalize), float(weight), P(ws), ws.numel(), P(gz), int(accumulate), P(phi),
+                          P(loss), _stream(dev))
+    return loss
+
+
+#: per device: the constant 1 the binary loss's `region + w * boundary` reads (unetseg_scale_grad's g)
+_ONE = {}
+
+
+def _one(dev):
+    """a device scalar 1, made once per device.  Made during a StepPlan recording it is not logged: the
+    recorded launches only read it, and it lives as long as the process (like ops.workspace's buffers)."""
+    t = _ONE.get(dev)
+    if t is None:
+        rec = _plan.RECORDING
+        if rec is not None:
+            rec.suspended += 1
+        try:
+            t = _ONE[dev] = torch.ones(1, dtype=torch.float32, device=dev)
+        finally:
+            if rec is not None:
+                rec.suspended -= 1
+    return t
+
+
+def _add_boundary(region, out, nch, tgt, gz, boundary, ignore_index, one):
+    """region + w * L with the boundary term's gradient added onto the region loss's gz (None: no gradient);
+    boundary = (weight > 0, normalize); `one` a device scalar 1"""
+    w, normalize = boundary
+    H, W = out.shape[-2], out.shape[-1]
+    bl = _boundary_forward(out, nch, tgt, H, W, 1, ignore_index, normalize, w, gz, 1)
+    total = torch.empty((), dtype=torch.float32, device=out.device)
+    lib.scale_grad(P(one), 1, P(region), 1.0, P(bl), float(w), P(total), _stream(out.device))
+    return total
+
+
+def _boundary_arg(weight, normalize):
+    """None for the default weight 0 (nothing is launched), else (weight, normalize)"""
+    weight = float(weight)
+    if weight < 0 or not math.isfinite(weight):
+        raise ValueError(f"boundary_weight must be a finite number >= 0, got {weight}")
+    return (weight, bool(normalize)) if weight > 0 else None
+
+
 class _SegLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(fctx, outputs, targets, kind, pos_weight, ignore_index=None):
+    def forward(fctx, outputs, targets, kind, pos_weight, ignore_index=None, boundary=None):
         out, tgt, _ = _prep(outputs, targets, ignore_index)
         B, nch = out.shape[0], out.shape[1]
         Pn = out[0, 0].numel()
         loss, gz = _seg_forward(kind, out, nch, tgt, B, Pn, pos_weight, outputs.requires_grad, ignore_index)
+        if boundary is not None:
+            loss = _add_boundary(loss, out, nch, tgt, gz if outputs.requires_grad else None, boundary, ignore_index,
+                                 _one(out.device))
         fctx.save_for_backward(gz)
         fctx.meta = (B, nch, Pn, outputs.shape, outputs.dtype)
+        return loss
+
+    @staticmethod
+    def backward(fctx, g):
+        (gz,) = fctx.saved_tensors
+        B, nch, Pn, shape, dtype = fctx.meta
+        g = g.detach().float().reshape(1).contiguous()
+        dout = torch.empty(shape, dtype=torch.float32, device=gz.device)
+        scratch = torch.empty_like(gz)
+        lib.dz_to_dout(P(gz), B, Pn, nch, P(g), 1.0, 0, 0.0, P(scratch), P(dout), _stream(gz.device))
+        return dout.to(dtype), None, None, None, None, None
+
+
+def binary_segmentation_loss(outputs, targets, loss_name, pos_weight=None, ignore_index=None, boundary_weight=0.0,
+                             boundary_normalize=True):
+    """utils/train_and_eval.py:155-182 on the HIP path.  With ignore_index the valid pixels are
+    flattened across the batch (BCE: their mean; Lovasz: see unetseg_masked_loss_fwd).
+    boundary_weight > 0 adds boundary_weight * boundary_loss(outputs, targets, ignore_index=ignore_index,
+    normalize=boundary_normalize); its gradient is added onto the region loss's before the one backward
+    launch.  A constant per run: a recorded step plan keeps the value it was recorded with."""
+    if outputs.dim() != 4 or outputs.size(1) != 2:
+        raise ValueError(f"Expected output shape (N,2,H,W), got {tuple(outputs.shape)}")
+    if loss_name not in ("bce", "lovasz_hinge"):
+        raise ValueError(f"Unsupported loss_name: {loss_name}")
+    return _SegLossFn.apply(outputs, targets, loss_name, pos_weight, ignore_index,
+                            _boundary_arg(boundary_weight, boundary_normalize))
+
+
+def _logits_4d(outputs):
+    if outputs.dim() == 3:
+        outputs = outputs.unsqueeze(1)
+    if outputs.dim() != 4 or outputs.size(1) not in (1, 2):
+        raise ValueError(f"Expected logits (B,2,H,W), (B,1,H,W) or (B,H,W), got {tuple(outputs.shape)}")
+    return outputs
+
+
+class _BoundaryLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, outputs, targets, c, ignore_index, normalize):
+        out, tgt, _ = _prep(outputs, targets, ignore_index)
+        B, nch, H, W = out.shape
+        if tuple(tgt.shape) != (B, H, W):
+            raise ValueError(f"boundary_loss: targets {tuple(targets.shape)} do not match logits {tuple(outputs.shape)}")
+        gz = torch.empty((B, H * W), dtype=torch.float32, device=out.device) if outputs.requires_grad else None
+        loss = _boundary_forward(out, nch, tgt, H, W, c, ignore_index, normalize, 1.0, gz, 0)
+        fctx.save_for_backward(gz)
+        fctx.meta = (B, nch, H * W, outputs.shape, outputs.dtype)
         return loss
 
     @staticmethod
@@ -152,14 +265,27 @@ class _SegLossFn(torch.autograd.Function):
         return dout.to(dtype), None, None, None, None
 
 
-def binary_segmentation_loss(outputs, targets, loss_name, pos_weight=None, ignore_index=None):
-    """utils/train_and_eval.py:155-182 on the HIP path.  With ignore_index the valid pixels are
-    flattened across the batch (BCE: their mean; Lovasz: see unetseg_masked_loss_fwd)."""
-    if outputs.dim() != 4 or outputs.size(1) != 2:
-        raise ValueError(f"Expected output shape (N,2,H,W), got {tuple(outputs.shape)}")
-    if loss_name not in ("bce", "lovasz_hinge"):
-        raise ValueError(f"Unsupported loss_name: {loss_name}")
-    return _SegLossFn.apply(outputs, targets, loss_name, pos_weight, ignore_index)
+def boundary_loss(outputs, targets, c=1, ignore_index=None, normalize=True):
+    """Boundary loss (Kervadec et al., MIDL 2019): mean over the non-ignored pixels of the batch of
+    sigmoid(z) * phi, phi the signed distance to the contour of {targets == c} (signed_distance).  outputs
+    [B,2,H,W] (z = o1 - o0), [B,1,H,W] or [B,H,W]; targets [B,H,W].  normalize divides by the image diagonal
+    sqrt(H^2 + W^2), so the value lies in [-1, 1] at every input size; False gives the paper's pixel units.
+    Meant to be added to a region loss with a small weight (boundary_weight= of the region losses)."""
+    return _BoundaryLossFn.apply(_logits_4d(outputs), targets, int(c), ignore_index, normalize)
+
+
+def signed_distance(targets, c=1, ignore_index=None):
+    """float32 [B,H,W]: the map phi of boundary_loss for integer targets [B,H,W] on the device: +distance to
+    the nearest pixel of class c outside it, -(distance to the nearest other pixel - 1) inside, 0 on ignored
+    pixels and in images that lack the set the distance would be taken to."""
+    if not targets.is_cuda or targets.dim() != 3:
+        raise ValueError("signed_distance: device targets [B,H,W] expected")
+    tgt = targets.detach().to(torch.int64).contiguous()
+    B, H, W = tgt.shape
+    out = torch.zeros((B, 1, H, W), dtype=torch.float32, device=tgt.device)
+    phi = torch.empty((B, H, W), dtype=torch.float32, device=tgt.device)
+    _boundary_forward(out, 1, tgt, H, W, int(c), ignore_index, False, 0.0, None, 0, phi)
+    return phi
 
 
 def seg_loss_1ch(logits, targets, kind):
@@ -171,12 +297,16 @@ def seg_loss_1ch(logits, targets, kind):
 
 class _MultiTaskFn(torch.autograd.Function):
     @staticmethod
-    def forward(fctx, seg, cls, seg_t, cls_t, w, kind):
+    def forward(fctx, seg, cls, seg_t, cls_t, w, kind, boundary=None):
         out, tgt, soft = _prep(seg, seg_t)
         B = out.shape[0]
         Pn = out[0].numel()
         dev = out.device
         seg_loss, gz = _seg_forward(kind, out, 1, tgt, B, Pn, None, True)
+        one = None
+        if boundary is not None:
+            one = torch.ones(1, dtype=torch.float32, device=dev)
+            seg_loss = _add_boundary(seg_loss, out, 1, tgt, gz, boundary, None, one)
         if kind == "bce":
             _poison(soft, seg_loss, gz)
         c = cls.detach().float().contiguous()
@@ -186,7 +316,8 @@ class _MultiTaskFn(torch.autograd.Function):
         lib.ce_fwd(P(c), P(ct), c.shape[0], c.shape[1], P(cls_loss), P(dlog), _stream(dev))
         total = torch.empty((), dtype=torch.float32, device=dev)
         # total = 1 * (seg + w * cls)  (device scalars, no host sync)
-        one = torch.ones(1, dtype=torch.float32, device=dev)
+        if one is None:
+            one = torch.ones(1, dtype=torch.float32, device=dev)
         lib.scale_grad(P(one), 1, P(seg_loss), 1.0, P(cls_loss), float(w), P(total), _stream(dev))
         fctx.save_for_backward(gz, dlog)
         fctx.meta = (B, Pn, seg.shape, float(w))
@@ -211,11 +342,15 @@ class _MultiTaskFn(torch.autograd.Function):
         lib.dz_to_dout(P(gz), B, Pn, 1, P(tmp), 1.0, 0, 0.0, P(scratch), P(dseg), st)
         dcls = torch.empty_like(dlog)
         lib.scale_grad(P(dlog), dlog.numel(), P(gt), w, P(gc), 1.0, P(dcls), st)
-        return dseg, dcls, None, None, None, None
+        return dseg, dcls, None, None, None, None, None
 
 
-def multitask_loss(seg_logits, cls_logits, seg_targets, cls_targets, cls_loss_weight=1.0, kind="bce"):
-    return _MultiTaskFn.apply(seg_logits, cls_logits, seg_targets, cls_targets, cls_loss_weight, kind)
+def multitask_loss(seg_logits, cls_logits, seg_targets, cls_targets, cls_loss_weight=1.0, kind="bce",
+                   boundary_weight=0.0, boundary_normalize=True):
+    """-> (total, seg_loss, cls_loss).  boundary_weight > 0 adds boundary_weight * boundary_loss of the seg
+    logits to seg_loss (and so to total), its gradient onto the seg term's (see binary_segmentation_loss)."""
+    return _MultiTaskFn.apply(seg_logits, cls_logits, seg_targets, cls_targets, cls_loss_weight, kind,
+                              _boundary_arg(boundary_weight, boundary_normalize))
 
 
 def binary_confusion(outputs, targets, conf=None, ignore_index=None):

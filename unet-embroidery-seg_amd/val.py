@@ -81,7 +81,8 @@ def val(args):
 
     if args.task == "binary":
         m = evaluate_binary(model, loader, device, loss_name=args.loss, pos_weight=None, ignore_index=None,
-                            boundary=boundary)
+                            boundary=boundary, boundary_weight=args.boundary_loss_weight,
+                            boundary_normalize=not args.boundary_loss_pixels)
         print(f"{LogColor.RED}Dice{LogColor.RESET}\t{LogColor.RED}IoU{LogColor.RESET}\t{LogColor.RED}Precision"
               f"{LogColor.RESET}\t{LogColor.RED}Recall{LogColor.RESET}\t{LogColor.RED}Accuracy{LogColor.RESET}")
         print(f"{m['Dice']:.4f}\t{m['IoU']:.4f}\t{m['Precision']:.4f}\t{m['Recall']:.4f}\t{m['Accuracy']:.4f}")
@@ -160,7 +161,17 @@ def parse_args(argv=None):
                    help="pixel tolerance of boundary precision / recall / F1")
     p.add_argument("--boundary-iou-d", default=0, type=int,
                    help="Boundary-IoU band width in pixels; 0 = 2 %% of the image diagonal")
-    return p.parse_args(argv)
+    p.add_argument("--boundary-loss-weight", default=0.0, type=float,
+                   help="the training run's boundary-loss weight, so the reported loss (m['Loss'], --task binary) is "
+                        "that objective; the multitask evaluation reports no loss")
+    p.add_argument("--boundary-loss-pixels", action="store_true",
+                   help="boundary loss in pixel units instead of fractions of the image diagonal")
+    args = p.parse_args(argv)
+    if args.boundary_loss_weight < 0:
+        p.error("--boundary-loss-weight must be >= 0")
+    if args.task == "multiclass" and (args.boundary_loss_weight > 0 or args.boundary_loss_pixels):
+        p.error("--boundary-loss-weight / --boundary-loss-pixels apply to --task binary and multitask only")
+    return args
 
 
 if __name__ == "__main__":
