@@ -553,6 +553,51 @@ int unetseg_boundary_loss_fwd(const float* out, int nch, const int64_t* tgt, int
                               size_t ws_bytes, float* gz, int accumulate, float* phi /* may be NULL */, float* loss,
                               void* stream);
 
+/* ---- soft skeleton and soft-clDice loss (Shit et al., CVPR 2021; no reference counterpart) -----------------
+ * x fp32 [H][W] in [0, 1]; windows are clipped to the image, a pixel outside it never takes part.
+ *   E(x)(q) = min over q and its four edge neighbours       window order: up, left, centre, right, down
+ *   D(x)(q) = max over the 3 x 3 neighbourhood of q         window order: row-major
+ *   O(x)    = D(E(x))
+ * Soft skeleton S_k(x), k = iters (the published soft_skel):
+ *   x_0 = x,            s_0 = relu(x_0 - O(x_0))
+ *   x_j = E(x_{j-1}),   d_j = relu(x_j - O(x_j)),   s_j = s_{j-1} + relu(d_j - s_{j-1} d_j)     j = 1 .. k
+ *   S_k = s_k
+ * Subgradients: relu'(a) = 1 iff a > 0; the gradient of a min or max window goes entirely to the first element
+ * that attains the extreme in window order.  x_j and O(x_j) are selections of input values (exact); each level
+ * rounds d_j and s_j in fp32 (four roundings, no fused multiply-add).
+ *
+ * unetseg_soft_skel_fwd: skel [N][H][W] = S_iters(x), x fp32 [N][H][W]; iters + 1 launches.  The levels the
+ * backward needs stay in ws (2 iters + 4 maps of N H W floats, each rounded up to 256 bytes).
+ * unetseg_soft_skel_bwd: gx [N][H][W] = the gradient of sum(gskel * S_iters(x)) by x, from the ws that
+ * unetseg_soft_skel_fwd filled for the same x, shape and iters; iters + 1 launches in gather form, every sum in a
+ * fixed order, no atomics.
+ *
+ * unetseg_cldice_fwd: out planar fp32 [B][nch][H][W] (nch 2: z = o1 - o0, nch 1: z = o0), tgt int64 [B][H][W],
+ * ignore_index (-1: none).  y = [t == 1], p = sigmoid(z); ignored pixels enter as y = 0, p = 0 and get zero
+ * gradient.  With every sum over the whole batch:
+ *   tprec = (sum S_k(p) y + smooth) / (sum S_k(p) + smooth)
+ *   tsens = (sum S_k(y) p + smooth) / (sum S_k(y) + smooth)
+ *   loss[0] = 1 - 2 tprec tsens / (tprec + tsens)                               (never weighted)
+ *   gz [B][H][W] (may be NULL) = weight * dloss/dz, dloss/dz = (dloss/dp) p (1 - p); added to gz when
+ *   accumulate != 0 (as a product, then a sum), so the term lands on a region loss's gz.
+ * The four sums are per-block double partials added by one block in a fixed order; the backward reads
+ * dloss/dtprec and dloss/dtsens from device scalars: no host wait.  loss, gz and the skeletons are bitwise
+ * reproducible.  The published defaults are iters = 3, smooth = 1.
+ *
+ * Checked before any launch: null pointers (gz of unetseg_cldice_fwd may be NULL), nch in {1, 2}, N / B, H, W > 0,
+ * 0 <= iters <= 64, smooth > 0, ignore_index != 1, ws_bytes, and a 16-byte aligned ws.  Nothing past the N H W
+ * elements of skel, gx and gz and past ws_bytes is written.  The workspace queries return 0 for a shape or iters
+ * they refuse. */
+size_t unetseg_soft_skel_workspace(int N, int H, int W, int iters); /* host only */
+int unetseg_soft_skel_fwd(const float* x, int N, int H, int W, int iters, void* ws, size_t ws_bytes, float* skel,
+                          void* stream);
+int unetseg_soft_skel_bwd(const float* x, int N, int H, int W, int iters, void* ws, size_t ws_bytes,
+                          const float* gskel, float* gx, void* stream);
+size_t unetseg_cldice_workspace(int B, int H, int W, int iters); /* host only */
+int unetseg_cldice_fwd(const float* out, int nch, const int64_t* tgt, int B, int H, int W,
+                       long ignore_index /* -1: none */, int iters, float smooth, float weight, void* ws,
+                       size_t ws_bytes, float* gz /* may be NULL */, int accumulate, float* loss, void* stream);
+
 /* ---- device augmentation of the loader (utils/hf_dataloader.py:67-105, 111-180, 183-213) -------
  * Replaces HFUnetDataset.get_random_data + preprocess + hf_unet_dataset_collate for one batch:
  * PIL BICUBIC image / NEAREST mask resize (bit-exact), flip, paste on the grey / zero canvas,

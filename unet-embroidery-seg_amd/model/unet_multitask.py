@@ -63,14 +63,18 @@ class MultiTaskLoss(nn.Module):
     """unet_multitask.py:109-139: total = seg_loss(seg.squeeze(1), y.float()) + w * CE(cls, c).
     seg_loss_fn None / nn.BCEWithLogitsLoss -> fused BCE kernel; lovasz_hinge_loss -> Lovasz kernel.
     boundary_weight > 0 adds that multiple of losses.boundary_loss of the seg logits to the seg term (no
-    reference counterpart; constant over a run)."""
+    reference counterpart; constant over a run); cldice_weight > 0 that multiple of losses.cldice_loss with
+    cldice_iters skeleton levels."""
 
-    def __init__(self, seg_loss_fn=None, cls_loss_weight=1.0, boundary_weight=0.0, boundary_normalize=True):
+    def __init__(self, seg_loss_fn=None, cls_loss_weight=1.0, boundary_weight=0.0, boundary_normalize=True,
+                 cldice_weight=0.0, cldice_iters=3):
         super().__init__()
         self.seg_loss_fn = seg_loss_fn or nn.BCEWithLogitsLoss()
         self.cls_loss_weight = cls_loss_weight
         self.boundary_weight = boundary_weight
         self.boundary_normalize = boundary_normalize
+        self.cldice_weight = cldice_weight
+        self.cldice_iters = cldice_iters
 
     def forward(self, seg_logits, cls_logits, seg_targets, cls_targets):
         fn = self.seg_loss_fn
@@ -83,4 +87,5 @@ class MultiTaskLoss(nn.Module):
         else:
             raise NotImplementedError(f"unsupported seg loss {fn}")
         return losses.multitask_loss(seg_logits, cls_logits, seg_targets, cls_targets, self.cls_loss_weight, kind,
-                                     self.boundary_weight, self.boundary_normalize)
+                                     self.boundary_weight, self.boundary_normalize, self.cldice_weight,
+                                     self.cldice_iters)

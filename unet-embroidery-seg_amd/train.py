@@ -170,7 +170,9 @@ def train(args):
             pos_weight = torch.tensor([float(args.pos_weight)], dtype=torch.float32, device=device)
 
     # the boundary-loss term of the binary and multitask objectives (training and the reported losses alike)
-    bnd = dict(boundary_weight=args.boundary_loss_weight, boundary_normalize=not args.boundary_loss_pixels)
+    # and the soft-clDice term
+    bnd = dict(boundary_weight=args.boundary_loss_weight, boundary_normalize=not args.boundary_loss_pixels,
+               cldice_weight=args.cldice_weight, cldice_iters=args.cldice_iters)
     criterion = None
     if args.task == "multitask":
         seg_fn = lovasz_hinge_loss if args.loss == "lovasz_hinge" else torch.nn.BCEWithLogitsLoss()
@@ -293,6 +295,10 @@ def parse_args(argv=None):
                         "multitask; constant over the run)")
     p.add_argument("--boundary-loss-pixels", action="store_true",
                    help="boundary loss in pixel units instead of fractions of the image diagonal")
+    p.add_argument("--cldice-weight", default=0.0, type=float,
+                   help="adds this multiple of the soft-clDice (centerline Dice) loss to the region loss (--task binary "
+                        "and multitask; constant over the run)")
+    p.add_argument("--cldice-iters", default=3, type=int, help="levels of the soft skeleton (0 .. 64)")
     p.add_argument("--pos-weight", default="auto")
     p.add_argument("--pos-weight-samples", default=80, type=int)
     p.add_argument("--use-dice", action=argparse.BooleanOptionalAction, default=True)
@@ -322,6 +328,12 @@ def parse_args(argv=None):
         p.error("--boundary-loss-weight must be >= 0")
     if args.task == "multiclass" and (args.boundary_loss_weight > 0 or args.boundary_loss_pixels):
         p.error("--boundary-loss-weight / --boundary-loss-pixels apply to --task binary and multitask only")
+    if args.cldice_weight < 0:
+        p.error("--cldice-weight must be >= 0")
+    if not 0 <= args.cldice_iters <= 64:
+        p.error("--cldice-iters must be 0 .. 64")
+    if args.task == "multiclass" and (args.cldice_weight > 0 or args.cldice_iters != 3):
+        p.error("--cldice-weight / --cldice-iters apply to --task binary and multitask only")
     if args.pos_weight == "":
         args.pos_weight = None
     return args

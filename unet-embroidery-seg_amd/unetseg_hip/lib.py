@@ -144,6 +144,11 @@ SIGNATURES = {
     "unetseg_boundary_counts": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, P, P]),
     "unetseg_boundary_loss_workspace": (SZ, [I, I, I]),
     "unetseg_boundary_loss_fwd": (I, [P, I, P, I, I, I, I, L, F, F, P, SZ, P, I, P, P, P]),
+    "unetseg_soft_skel_workspace": (SZ, [I, I, I, I]),
+    "unetseg_soft_skel_fwd": (I, [P, I, I, I, I, P, SZ, P, P]),
+    "unetseg_soft_skel_bwd": (I, [P, I, I, I, I, P, SZ, P, P, P]),
+    "unetseg_cldice_workspace": (SZ, [I, I, I, I]),
+    "unetseg_cldice_fwd": (I, [P, I, P, I, I, I, L, I, F, F, P, SZ, P, I, P, P]),
 }
 
 #: functions returning a value rather than a status (no RuntimeError on non-zero)

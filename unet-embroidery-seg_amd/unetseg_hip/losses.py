@@ -9,6 +9,8 @@ Multiclass task: ce_loss / focal_loss / dice_loss (one fused kernel pair) and lo
 multiclass form of the Lovasz hinge, on the same segmented radix sort).
 boundary_loss / signed_distance: the distance-map loss of Kervadec et al. (MIDL 2019) on the exact GPU distance
 transform; boundary_weight= of binary_segmentation_loss and multitask_loss adds it to the region loss.
+soft_skeleton / cldice_loss: the soft skeleton and the centerline Dice of Shit et al. (CVPR 2021) on min / max
+stencil kernels with a gather-form backward; cldice_weight= of the same two losses adds it to the region loss.
 """
 from __future__ import annotations
 
@@ -193,9 +195,47 @@ def _boundary_arg(weight, normalize):
     return (weight, bool(normalize)) if weight > 0 else None
 
 
+def _cldice_forward(out, nch, tgt, H, W, ignore_index, iters, smooth, weight, gz, accumulate):
+    """unetseg_cldice_fwd on prepared tensors -> the unweighted loss (device scalar); gz (may be None) gets,
+    or with `accumulate` is added, weight * dL/dz"""
+    dev = out.device
+    B = out.shape[0]
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    ws = workspace(_q("cldice_workspace", B, H, W, int(iters)), dev)
+    lib.cldice_fwd(P(out), nch, P(tgt), B, H, W, -1 if ignore_index is None else int(ignore_index), int(iters),
+                   float(smooth), float(weight), P(ws), ws.numel(), P(gz), int(accumulate), P(loss), _stream(dev))
+    return loss
+
+
+def _add_cldice(region, out, nch, tgt, gz, cldice, ignore_index, one):
+    """region + w * L with the clDice term's gradient added onto the region loss's gz (None: no gradient);
+    cldice = (weight > 0, iters); `one` a device scalar 1"""
+    w, iters = cldice
+    H, W = out.shape[-2], out.shape[-1]
+    cl = _cldice_forward(out, nch, tgt, H, W, ignore_index, iters, 1.0, w, gz, 1)
+    total = torch.empty((), dtype=torch.float32, device=out.device)
+    lib.scale_grad(P(one), 1, P(region), 1.0, P(cl), float(w), P(total), _stream(out.device))
+    return total
+
+
+def _check_iters(iters):
+    if int(iters) != iters or not 0 <= int(iters) <= 64:
+        raise ValueError(f"cldice iters must be an integer in 0 .. 64, got {iters}")
+    return int(iters)
+
+
+def _cldice_arg(weight, iters):
+    """None for the default weight 0 (nothing is launched), else (weight, iters)"""
+    weight = float(weight)
+    if weight < 0 or not math.isfinite(weight):
+        raise ValueError(f"cldice_weight must be a finite number >= 0, got {weight}")
+    iters = _check_iters(iters)
+    return (weight, iters) if weight > 0 else None
+
+
 class _SegLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(fctx, outputs, targets, kind, pos_weight, ignore_index=None, boundary=None):
+    def forward(fctx, outputs, targets, kind, pos_weight, ignore_index=None, boundary=None, cldice=None):
         out, tgt, _ = _prep(outputs, targets, ignore_index)
         B, nch = out.shape[0], out.shape[1]
         Pn = out[0, 0].numel()
@@ -203,6 +243,9 @@ class _SegLossFn(torch.autograd.Function):
         if boundary is not None:
             loss = _add_boundary(loss, out, nch, tgt, gz if outputs.requires_grad else None, boundary, ignore_index,
                                  _one(out.device))
+        if cldice is not None:
+            loss = _add_cldice(loss, out, nch, tgt, gz if outputs.requires_grad else None, cldice, ignore_index,
+                               _one(out.device))
         fctx.save_for_backward(gz)
         fctx.meta = (B, nch, Pn, outputs.shape, outputs.dtype)
         return loss
@@ -215,22 +258,25 @@ class _SegLossFn(torch.autograd.Function):
         dout = torch.empty(shape, dtype=torch.float32, device=gz.device)
         scratch = torch.empty_like(gz)
         lib.dz_to_dout(P(gz), B, Pn, nch, P(g), 1.0, 0, 0.0, P(scratch), P(dout), _stream(gz.device))
-        return dout.to(dtype), None, None, None, None, None
+        return dout.to(dtype), None, None, None, None, None, None
 
 
 def binary_segmentation_loss(outputs, targets, loss_name, pos_weight=None, ignore_index=None, boundary_weight=0.0,
-                             boundary_normalize=True):
+                             boundary_normalize=True, cldice_weight=0.0, cldice_iters=3):
     """utils/train_and_eval.py:155-182 on the HIP path.  With ignore_index the valid pixels are
     flattened across the batch (BCE: their mean; Lovasz: see unetseg_masked_loss_fwd).
     boundary_weight > 0 adds boundary_weight * boundary_loss(outputs, targets, ignore_index=ignore_index,
     normalize=boundary_normalize); its gradient is added onto the region loss's before the one backward
-    launch.  A constant per run: a recorded step plan keeps the value it was recorded with."""
+    launch.  A constant per run: a recorded step plan keeps the value it was recorded with.
+    cldice_weight > 0 adds cldice_weight * cldice_loss(outputs, targets, iters=cldice_iters,
+    ignore_index=ignore_index) the same way; both terms may be set."""
     if outputs.dim() != 4 or outputs.size(1) != 2:
         raise ValueError(f"Expected output shape (N,2,H,W), got {tuple(outputs.shape)}")
     if loss_name not in ("bce", "lovasz_hinge"):
         raise ValueError(f"Unsupported loss_name: {loss_name}")
     return _SegLossFn.apply(outputs, targets, loss_name, pos_weight, ignore_index,
-                            _boundary_arg(boundary_weight, boundary_normalize))
+                            _boundary_arg(boundary_weight, boundary_normalize),
+                            _cldice_arg(cldice_weight, cldice_iters))
 
 
 def _logits_4d(outputs):
@@ -288,6 +334,76 @@ def signed_distance(targets, c=1, ignore_index=None):
     return phi
 
 
+class _ClDiceLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, outputs, targets, iters, smooth, ignore_index):
+        out, tgt, _ = _prep(outputs, targets, ignore_index)
+        B, nch, H, W = out.shape
+        if tuple(tgt.shape) != (B, H, W):
+            raise ValueError(f"cldice_loss: targets {tuple(targets.shape)} do not match logits {tuple(outputs.shape)}")
+        gz = torch.empty((B, H * W), dtype=torch.float32, device=out.device) if outputs.requires_grad else None
+        loss = _cldice_forward(out, nch, tgt, H, W, ignore_index, iters, smooth, 1.0, gz, 0)
+        fctx.save_for_backward(gz)
+        fctx.meta = (B, nch, H * W, outputs.shape, outputs.dtype)
+        return loss
+
+    @staticmethod
+    def backward(fctx, g):
+        (gz,) = fctx.saved_tensors
+        B, nch, Pn, shape, dtype = fctx.meta
+        g = g.detach().float().reshape(1).contiguous()
+        dout = torch.empty(shape, dtype=torch.float32, device=gz.device)
+        scratch = torch.empty_like(gz)
+        lib.dz_to_dout(P(gz), B, Pn, nch, P(g), 1.0, 0, 0.0, P(scratch), P(dout), _stream(gz.device))
+        return dout.to(dtype), None, None, None, None
+
+
+def cldice_loss(outputs, targets, iters=3, smooth=1.0, ignore_index=None):
+    """Soft clDice (Shit et al., CVPR 2021): 1 - the harmonic mean of the topology precision
+    (sum S(p) y + smooth) / (sum S(p) + smooth) and sensitivity (sum S(y) p + smooth) / (sum S(y) + smooth), with
+    p = sigmoid(z), y = [targets == 1], S the soft skeleton of `iters` levels (soft_skeleton) and the sums over
+    the whole batch.  outputs [B,2,H,W] (z = o1 - o0), [B,1,H,W] or [B,H,W]; targets [B,H,W]; pixels whose target
+    is ignore_index enter as p = y = 0 and get no gradient.  Meant to be added to a region loss
+    (cldice_weight= of the region losses)."""
+    smooth = float(smooth)
+    if not (smooth > 0 and math.isfinite(smooth)):
+        raise ValueError(f"cldice_loss: smooth must be a finite number > 0, got {smooth}")
+    return _ClDiceLossFn.apply(_logits_4d(outputs), targets, _check_iters(iters), smooth, ignore_index)
+
+
+class _SoftSkelFn(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, x, iters):
+        xc = x.detach().contiguous()
+        N, H, W = (xc.shape[0], xc.shape[-2], xc.shape[-1])
+        dev = xc.device
+        # its own buffer, not ops.workspace: the levels must outlive the forward
+        ws = torch.empty(max(_q("soft_skel_workspace", N, H, W, iters), 16), dtype=torch.uint8, device=dev)
+        skel = torch.empty_like(xc)
+        lib.soft_skel_fwd(P(xc), N, H, W, iters, P(ws), ws.numel(), P(skel), _stream(dev))
+        fctx.save_for_backward(xc, ws)
+        fctx.meta = (N, H, W, iters)
+        return skel
+
+    @staticmethod
+    def backward(fctx, g):
+        xc, ws = fctx.saved_tensors
+        N, H, W, iters = fctx.meta
+        gc = g.detach().float().contiguous()
+        gx = torch.empty_like(xc)
+        lib.soft_skel_bwd(P(xc), N, H, W, iters, P(ws), ws.numel(), P(gc), P(gx), _stream(xc.device))
+        return gx, None
+
+
+def soft_skeleton(x, iters=3):
+    """The soft skeleton S_iters(x) of Shit et al. (CVPR 2021) for fp32 device maps [N,H,W] or [N,1,H,W] with
+    values in [0, 1]: iterated min (cross) / max (3 x 3) pooling, differentiable with the subgradient rules of
+    include/unetseg_hip.h (a window's gradient goes to the first element that attains its extreme)."""
+    if not x.is_cuda or x.dtype != torch.float32 or not (x.dim() == 3 or (x.dim() == 4 and x.size(1) == 1)):
+        raise ValueError("soft_skeleton: fp32 device maps [N,H,W] or [N,1,H,W] expected")
+    return _SoftSkelFn.apply(x, _check_iters(iters))
+
+
 def seg_loss_1ch(logits, targets, kind):
     """loss on [B,1,H,W] (or [B,H,W]) logits, e.g. MultiTaskLoss's seg term"""
     if logits.dim() == 3:
@@ -297,7 +413,7 @@ def seg_loss_1ch(logits, targets, kind):
 
 class _MultiTaskFn(torch.autograd.Function):
     @staticmethod
-    def forward(fctx, seg, cls, seg_t, cls_t, w, kind, boundary=None):
+    def forward(fctx, seg, cls, seg_t, cls_t, w, kind, boundary=None, cldice=None):
         out, tgt, soft = _prep(seg, seg_t)
         B = out.shape[0]
         Pn = out[0].numel()
@@ -307,6 +423,10 @@ class _MultiTaskFn(torch.autograd.Function):
         if boundary is not None:
             one = torch.ones(1, dtype=torch.float32, device=dev)
             seg_loss = _add_boundary(seg_loss, out, 1, tgt, gz, boundary, None, one)
+        if cldice is not None:
+            if one is None:
+                one = torch.ones(1, dtype=torch.float32, device=dev)
+            seg_loss = _add_cldice(seg_loss, out, 1, tgt, gz, cldice, None, one)
         if kind == "bce":
             _poison(soft, seg_loss, gz)
         c = cls.detach().float().contiguous()
@@ -342,15 +462,17 @@ class _MultiTaskFn(torch.autograd.Function):
         lib.dz_to_dout(P(gz), B, Pn, 1, P(tmp), 1.0, 0, 0.0, P(scratch), P(dseg), st)
         dcls = torch.empty_like(dlog)
         lib.scale_grad(P(dlog), dlog.numel(), P(gt), w, P(gc), 1.0, P(dcls), st)
-        return dseg, dcls, None, None, None, None, None
+        return dseg, dcls, None, None, None, None, None, None
 
 
 def multitask_loss(seg_logits, cls_logits, seg_targets, cls_targets, cls_loss_weight=1.0, kind="bce",
-                   boundary_weight=0.0, boundary_normalize=True):
+                   boundary_weight=0.0, boundary_normalize=True, cldice_weight=0.0, cldice_iters=3):
     """-> (total, seg_loss, cls_loss).  boundary_weight > 0 adds boundary_weight * boundary_loss of the seg
-    logits to seg_loss (and so to total), its gradient onto the seg term's (see binary_segmentation_loss)."""
+    logits to seg_loss (and so to total), its gradient onto the seg term's (see binary_segmentation_loss);
+    cldice_weight > 0 does the same with cldice_loss(seg logits, seg targets, iters=cldice_iters)."""
     return _MultiTaskFn.apply(seg_logits, cls_logits, seg_targets, cls_targets, cls_loss_weight, kind,
-                              _boundary_arg(boundary_weight, boundary_normalize))
+                              _boundary_arg(boundary_weight, boundary_normalize),
+                              _cldice_arg(cldice_weight, cldice_iters))
 
 
 def binary_confusion(outputs, targets, conf=None, ignore_index=None):

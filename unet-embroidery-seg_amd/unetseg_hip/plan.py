@@ -46,7 +46,8 @@ RECORDING = None
 # C-ABI entry points that only answer host-side shape questions (no device work): not logged
 _PURE = frozenset(n for n in _libmod.VALUE_FUNCS if n not in ("conv2d_fwd_mask", "conv2d_dgrad_post",
                                                                  "conv2d_dgrad_post_res")) | {
-    "last_error", "device_arch", "abi_version", "boundary_loss_workspace"}
+    "last_error", "device_arch", "abi_version", "boundary_loss_workspace", "soft_skel_workspace",
+    "cldice_workspace"}
 
 
 class Dyn(int):

@@ -111,17 +111,19 @@ def binary_segmentation_metrics(tp: float, fp: float, fn: float, tn: float, eps:
 
 
 def binary_segmentation_loss(outputs, targets, loss_name: str, pos_weight=None, ignore_index=None, boundary_weight=0.0,
-                             boundary_normalize=True):
+                             boundary_normalize=True, cldice_weight=0.0, cldice_iters=3):
     """train_and_eval.py:155-182 -> fused HIP kernel (2-class difference fused); boundary_weight > 0 adds the
-    boundary loss (losses.boundary_loss) with that weight."""
+    boundary loss (losses.boundary_loss) with that weight, cldice_weight > 0 the soft clDice
+    (losses.cldice_loss, cldice_iters skeleton levels)."""
     return losses.binary_segmentation_loss(outputs, targets, loss_name, pos_weight, ignore_index, boundary_weight,
-                                           boundary_normalize)
+                                           boundary_normalize, cldice_weight, cldice_iters)
 
 
 def train_one_epoch_binary(model, optimizer, train_loader, device, loss_name: str, pos_weight, gpu_used, scaler, epoch,
                            train_epoch, ignore_index=None, max_batches=None, boundary_weight=0.0,
-                           boundary_normalize=True):
-    """train_and_eval.py:185-263; boundary_weight: see binary_segmentation_loss (constant over the run)"""
+                           boundary_normalize=True, cldice_weight=0.0, cldice_iters=3):
+    """train_and_eval.py:185-263; boundary_weight, cldice_weight: see binary_segmentation_loss (constants of
+    the run)"""
     epoch_loss = torch.zeros((), dtype=torch.float64, device=device)
     lag = _LaggedLoss()
     seen_batches = 0
@@ -135,14 +137,14 @@ def train_one_epoch_binary(model, optimizer, train_loader, device, loss_name: st
         if scaler is None:
             outputs = model_train(imgs)
             loss = binary_segmentation_loss(outputs, pngs, loss_name, pos_weight, ignore_index, boundary_weight,
-                                            boundary_normalize)
+                                            boundary_normalize, cldice_weight, cldice_iters)
             loss.backward()
             optimizer.step()
         else:
             with autocast(device_type=device.type, enabled=True):
                 outputs = model_train(imgs)
                 loss = binary_segmentation_loss(outputs, pngs, loss_name, pos_weight, ignore_index, boundary_weight,
-                                                boundary_normalize)
+                                                boundary_normalize, cldice_weight, cldice_iters)
             scaler.scale(loss).backward()
             scaler.step(optimizer)
             scaler.update()
@@ -166,9 +168,9 @@ def _boundary_acc(boundary, classes=(1,), ignore_index=None):
 
 
 def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignore_index=None, max_batches=None,
-                    boundary=None, boundary_weight=0.0, boundary_normalize=True):
+                    boundary=None, boundary_weight=0.0, boundary_normalize=True, cldice_weight=0.0, cldice_iters=3):
     """train_and_eval.py:266-305: eval-mode fp32 forward, global tp/fp/fn/tn, metrics with eps 1e-7.
-    boundary_weight: the training objective's boundary-loss weight, so the reported loss is that objective.
+    boundary_weight, cldice_weight: the training objective's extra terms, so the reported loss is that objective.
     boundary: None, or {"tolerance": px, "biou_d": px or None} to add the boundary metrics of class 1
     (unetseg_hip/boundary.py), counted on the device and read with the confusion counts."""
     model_eval = model.eval().to(device)
@@ -181,7 +183,7 @@ def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignor
             imgs, pngs = batch[0].to(device), batch[1].to(device)
             outputs = model_eval(imgs)
             loss = binary_segmentation_loss(outputs, pngs, loss_name, pos_weight, ignore_index, boundary_weight,
-                                            boundary_normalize)
+                                            boundary_normalize, cldice_weight, cldice_iters)
             total_loss += loss
             losses.binary_confusion(outputs, pngs, conf, ignore_index)
             if bacc is not None:

@@ -82,7 +82,8 @@ def val(args):
     if args.task == "binary":
         m = evaluate_binary(model, loader, device, loss_name=args.loss, pos_weight=None, ignore_index=None,
                             boundary=boundary, boundary_weight=args.boundary_loss_weight,
-                            boundary_normalize=not args.boundary_loss_pixels)
+                            boundary_normalize=not args.boundary_loss_pixels, cldice_weight=args.cldice_weight,
+                            cldice_iters=args.cldice_iters)
         print(f"{LogColor.RED}Dice{LogColor.RESET}\t{LogColor.RED}IoU{LogColor.RESET}\t{LogColor.RED}Precision"
               f"{LogColor.RESET}\t{LogColor.RED}Recall{LogColor.RESET}\t{LogColor.RED}Accuracy{LogColor.RESET}")
         print(f"{m['Dice']:.4f}\t{m['IoU']:.4f}\t{m['Precision']:.4f}\t{m['Recall']:.4f}\t{m['Accuracy']:.4f}")
@@ -166,7 +167,16 @@ def parse_args(argv=None):
                         "that objective; the multitask evaluation reports no loss")
     p.add_argument("--boundary-loss-pixels", action="store_true",
                    help="boundary loss in pixel units instead of fractions of the image diagonal")
+    p.add_argument("--cldice-weight", default=0.0, type=float,
+                   help="the training run's soft-clDice weight, so the reported loss (--task binary) is that objective")
+    p.add_argument("--cldice-iters", default=3, type=int, help="levels of the soft skeleton (0 .. 64)")
     args = p.parse_args(argv)
+    if args.cldice_weight < 0:
+        p.error("--cldice-weight must be >= 0")
+    if not 0 <= args.cldice_iters <= 64:
+        p.error("--cldice-iters must be 0 .. 64")
+    if args.task == "multiclass" and (args.cldice_weight > 0 or args.cldice_iters != 3):
+        p.error("--cldice-weight / --cldice-iters apply to --task binary and multitask only")
     if args.boundary_loss_weight < 0:
         p.error("--boundary-loss-weight must be >= 0")
     if args.task == "multiclass" and (args.boundary_loss_weight > 0 or args.boundary_loss_pixels):
