@@ -598,6 +598,51 @@ int unetseg_cldice_fwd(const float* out, int nch, const int64_t* tgt, int B, int
                        long ignore_index /* -1: none */, int iters, float smooth, float weight, void* ws,
                        size_t ws_bytes, float* gz /* may be NULL */, int accumulate, float* loss, void* stream);
 
+/* ---- hard skeleton (thinning) and the clDice metric's counts (Shit et al., CVPR 2021, section 3; no
+ * ---- reference counterpart) ------------------------------------------------------------------------
+ * Thinning is Guo & Hall's two-subiteration algorithm (CACM 32(3), 1989, algorithm A1), per class of a class
+ * map cls int32 [N][H][W].  Class 0 is background; the classes are 1 .. 255, any other value counts as
+ * background and comes out 0.  A neighbour of pixel q counts as set iff it lies inside the image and has the
+ * class of q: thinning a multi-class map is the union of thinning each class mask on its own.  Neighbours of
+ * (y, x):
+ *   P9 (y-1, x-1)   P2 (y-1, x)   P3 (y-1, x+1)
+ *   P8 (y,   x-1)                 P4 (y,   x+1)
+ *   P7 (y+1, x-1)   P6 (y+1, x)   P5 (y+1, x+1)
+ *   C  = (!P2 & (P3|P4)) + (!P4 & (P5|P6)) + (!P6 & (P7|P8)) + (!P8 & (P9|P2))
+ *   N1 = (P9|P2) + (P3|P4) + (P5|P6) + (P7|P8)
+ *   N2 = (P2|P3) + (P4|P5) + (P6|P7) + (P8|P9)
+ *   N  = min(N1, N2)
+ * A subiteration deletes (sets to 0) every non-zero pixel with C == 1, 2 <= N <= 3 and m == 0; the first
+ * subiteration of a pass has m = (P6|P7|!P9) & P8, the second m = (P2|P3|!P5) & P4.  Each subiteration is
+ * evaluated on the map as it stood before it.  A pass is the two subiterations in that order; thinning of an
+ * image ends after the first pass that deletes nothing, or after max_passes passes.
+ *
+ * unetseg_skel_thin: out = cls with the deleted pixels set to 0; unconverged int32 [N] (may be NULL) = 1 iff
+ * the last pass executed on image n still deleted a pixel.  max_passes = 0 runs no pass: out = cls (classes
+ * outside 1 .. 255 zeroed) and unconverged = 0.  2 + ceil(max_passes / passes_per_launch) launches whatever
+ * the data; none waits on the host; an image that has converged costs one flag read per block and launch.
+ * ws: unetseg_skel_workspace(N, H, W) bytes, 16-byte aligned.  The result is bitwise reproducible and shows
+ * neither the tile nor passes_per_launch.
+ *
+ * unetseg_skel_counts: out int64 [6] += over the pixels whose target is not `ignore` (-1: none)
+ *   [0] #(skel_pred == c and target == c)   [1] #(skel_pred == c)
+ *   [2] #(skel_target == c and pred == c)   [3] #(skel_target == c)
+ *   [4] the number of images n with unconv_pred[n] | unconv_target[n]   [5] N
+ * skel_pred / skel_target are unetseg_skel_thin's results for pred / target (with the ignored pixels set to 0
+ * in both before thinning), unconv_* its unconverged arrays.
+ *
+ * Checked before any launch: null pointers (unconverged of unetseg_skel_thin may be NULL), N, H, W > 0,
+ * max_passes >= 0, ws_bytes and a 16-byte aligned ws, 1 <= c <= 255, ignore != c.  The workspace query returns 0
+ * for a shape it refuses. */
+/* host only: the tile seams lie at the multiples of *tw and *th; one launch runs *passes_per_launch passes */
+int unetseg_skel_tile(int* tw, int* th, int* passes_per_launch);
+size_t unetseg_skel_workspace(int N, int H, int W); /* host only */
+int unetseg_skel_thin(const int32_t* cls, int N, int H, int W, int max_passes, int32_t* out,
+                      int32_t* unconverged /* [N], may be NULL */, void* ws, size_t ws_bytes, void* stream);
+int unetseg_skel_counts(const int32_t* pred, const int32_t* target, const int32_t* skel_pred,
+                        const int32_t* skel_target, const int32_t* unconv_pred, const int32_t* unconv_target, int N,
+                        int H, int W, int c, int ignore, int64_t* out /* [6], accumulates */, void* stream);
+
 /* ---- device augmentation of the loader (utils/hf_dataloader.py:67-105, 111-180, 183-213) -------
  * Replaces HFUnetDataset.get_random_data + preprocess + hf_unet_dataset_collate for one batch:
  * PIL BICUBIC image / NEAREST mask resize (bit-exact), flip, paste on the grey / zero canvas,

@@ -27,6 +27,12 @@ is filled with the class above it (csrc/ccl.hip, unetseg_hip/ccl.py).  ``--conne
 that of the non-zero classes; the background takes the dual.  ``--components`` also writes
 ``<name>_components.json`` beside the mask: class, area and box of every component of the cleaned
 map.  The defaults (0, 0, 8, off) launch nothing and leave the output as it was.
+
+``--skeleton`` (no reference counterpart) thins the cleaned label map on the device (csrc/skeleton.hip,
+unetseg_hip/skeleton.py: Guo-Hall thinning per class) and writes the centerlines to ``<name>_skeleton.png``
+beside the mask, in the class colours on black; with ``--components`` every entry of the component list
+gains ``skeleton_px``, the number of skeleton pixels of that component.  Off by default: nothing is launched
+and the other outputs stay byte for byte what they were.
 """
 from __future__ import annotations
 
@@ -47,7 +53,7 @@ import torch  # noqa: E402
 from PIL import Image  # noqa: E402
 
 from model.model_factory import SUPPORTED_MODELS, build_model  # noqa: E402
-from unetseg_hip import ccl  # noqa: E402
+from unetseg_hip import ccl, skeleton as skel  # noqa: E402
 from unetseg_hip.lib import lib  # noqa: E402
 from unetseg_hip.tta import MODES as TTA_MODES, TTA  # noqa: E402
 from utils import tiling  # noqa: E402
@@ -96,18 +102,30 @@ def letterbox(image, device):
     return x, nw, nh
 
 
-def finish_labels(labels, min_area=0, max_hole=0, connectivity=8, components=False):
+def finish_labels(labels, min_area=0, max_hole=0, connectivity=8, components=False, skeleton=False):
     """the device label map cleaned (unetseg_hip.ccl.clean) and downloaded; with ``components`` also the
-    cleaned map's component table int32 [K][7], (image, class, area, ymin, xmin, ymax, xmax)"""
+    cleaned map's component table int32 [K][7], (image, class, area, ymin, xmin, ymax, xmax); with
+    ``skeleton`` the cleaned map is thinned on the device (unetseg_hip.skeleton.thin) and the skeleton map
+    int32 [H][W] comes last, and the table has an eighth column, the component's skeleton pixels"""
     labels = ccl.clean(labels, min_area, max_hole, connectivity)
+    if not skeleton:
+        if components:
+            return labels.cpu().numpy(), ccl.components(labels, connectivity).cpu().numpy()
+        return labels.cpu().numpy()
+    sk, unconverged = skel.thin(labels, return_unconverged=True)
+    done = (labels.cpu().numpy(),)
     if components:
-        return labels.cpu().numpy(), ccl.components(labels, connectivity).cpu().numpy()
-    return labels.cpu().numpy()
+        done += (ccl.components(labels, connectivity, skeleton=sk).cpu().numpy(),)
+    done += (sk.cpu().numpy(),)
+    if int(unconverged.sum().item()):  # read after the downloads above: no extra wait
+        raise RuntimeError(f"thinning had not converged after {skel.default_max_passes(*labels.shape[-2:])} passes")
+    return done
 
 
-def predict_labels(model, image, device, min_area=0, max_hole=0, connectivity=8, components=False):
+def predict_labels(model, image, device, min_area=0, max_hole=0, connectivity=8, components=False, skeleton=False):
     """predict.py:72-93: the argmax label map int32 [H][W] at the image's original size, cleaned as
-    ``finish_labels`` says (and followed by the component table when ``components`` is set)"""
+    ``finish_labels`` says (and followed by the component table when ``components`` is set, and by the
+    skeleton map when ``skeleton`` is)"""
     x, nw, nh = letterbox(image, device)
     with torch.no_grad():
         pr = model(x)[0].float().contiguous()
@@ -116,17 +134,17 @@ def predict_labels(model, image, device, min_area=0, max_hole=0, connectivity=8,
     labels = torch.empty(oh, ow, dtype=torch.int32, device=device)
     lib.softmax_resize_argmax(pr.data_ptr(), C, H, W, (INPUT_SHAPE[0] - nh) // 2, (INPUT_SHAPE[1] - nw) // 2, nh, nw,
                               oh, ow, labels.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
-    return finish_labels(labels, min_area, max_hole, connectivity, components)
+    return finish_labels(labels, min_area, max_hole, connectivity, components, skeleton)
 
 
 def predict_labels_tiled(model, image, device, tile=512, overlap=64, tile_batch=8, bf16=False, return_probs=False,
-                         min_area=0, max_hole=0, connectivity=8, components=False):
+                         min_area=0, max_hole=0, connectivity=8, components=False, skeleton=False):
     """the argmax label map int32 [H][W] of the image at its native resolution: overlapping tiles
     (utils/tiling.py) gathered on the device, ``model`` (any callable [B,3,t,t] fp32 -> [B,C,t,t]
     logits, C >= 2) run over ranges of ``tile_batch`` tiles, the window-weighted softmax of every tile
     accumulated in ascending tile order and normalised, the label map cleaned as ``finish_labels`` says.
     With ``return_probs`` also the blended fp32 probabilities [C][H][W] (of the map before cleaning);
-    with ``components`` the component table comes last."""
+    with ``components`` the component table comes after those, and with ``skeleton`` the skeleton map last."""
     tiling.check(tile, overlap)
     rgb = np.array(image, np.uint8)  # a writable C-contiguous copy (a PIL image's buffer is read-only)
     if rgb.ndim != 3 or rgb.shape[2] != 3:
@@ -156,9 +174,11 @@ def predict_labels_tiled(model, image, device, tile=512, overlap=64, tile_batch=
     probs = torch.empty_like(acc) if return_probs else None
     lib.tile_finish(acc.data_ptr(), acc.shape[0], H, W, tile, overlap, probs.data_ptr() if return_probs else None,
                     labels.data_ptr(), st)
-    done = finish_labels(labels, min_area, max_hole, connectivity, components)
+    done = finish_labels(labels, min_area, max_hole, connectivity, components, skeleton)
     if return_probs:
-        return (done[0], probs.cpu().numpy(), done[1]) if components else (done, probs.cpu().numpy())
+        if components or skeleton:
+            return (done[0], probs.cpu().numpy()) + tuple(done[1:])
+        return done, probs.cpu().numpy()
     return done
 
 
@@ -186,9 +206,10 @@ def check_clean(min_area, max_hole, connectivity):
 
 
 def components_json(table):
-    """the component table as the list ``--components`` writes: class, area, bbox [x0, y0, x1, y1], in table order"""
-    return [{"class": int(c), "area": int(a), "bbox": [int(x0), int(y0), int(x1), int(y1)]}
-            for _, c, a, y0, x0, y1, x1 in table]
+    """the component table as the list ``--components`` writes: class, area, bbox [x0, y0, x1, y1], in table order;
+    a table with the skeleton column adds skeleton_px"""
+    return [dict({"class": int(r[1]), "area": int(r[2]), "bbox": [int(r[4]), int(r[3]), int(r[6]), int(r[5])]},
+                 **({"skeleton_px": int(r[7])} if len(r) > 7 else {})) for r in table]
 
 
 def blend(old, seg, alpha=0.7):
@@ -199,9 +220,10 @@ def blend(old, seg, alpha=0.7):
 
 
 def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, device=None, tile=0, overlap=64,
-                 tile_batch=8, bf16=False, min_area=0, max_hole=0, connectivity=8, components=False):
+                 tile_batch=8, bf16=False, min_area=0, max_hole=0, connectivity=8, components=False, skeleton=False):
     """predict.py:41-109; tile > 0 takes the label map from predict_labels_tiled; ``components`` writes
-    the cleaned map's component list to ``<name>_components.json`` beside the mask"""
+    the cleaned map's component list to ``<name>_components.json`` beside the mask, ``skeleton`` the cleaned
+    map's centerlines to ``<name>_skeleton.png``"""
     try:
         image = Image.open(file_path)
     except (FileNotFoundError, IOError) as e:
@@ -211,7 +233,8 @@ def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, devic
     image = cvtColor(image)
     old_img = image.copy()
     # only the cleanup options that are set: without any, the two calls are what they were before cleanup existed
-    post = {k: v for k, v in (("min_area", min_area), ("max_hole", max_hole), ("components", components)) if v}
+    post = {k: v for k, v in (("min_area", min_area), ("max_hole", max_hole), ("components", components),
+                                  ("skeleton", skeleton)) if v}
     if post:
         post["connectivity"] = connectivity
     if tile:
@@ -219,7 +242,10 @@ def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, devic
                                   **post)
     else:
         pr = predict_labels(model, image, device, **post)
-    if components:
+    if skeleton:
+        table, sk_map = pr[1] if components else None, pr[-1]
+        pr = pr[0]
+    elif components:
         pr, table = pr
     oh, ow = pr.shape
     seg_img = np.reshape(np.array(colors_for(num_classes), np.uint8)[np.reshape(pr, [-1])], [oh, ow, -1])
@@ -230,6 +256,10 @@ def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, devic
     if components:
         with open(save_path[:-len("_mask.png")] + "_components.json", "w") as f:
             json.dump(components_json(table), f)
+    if skeleton:
+        palette = np.array(colors_for(num_classes), np.uint8)
+        palette[0] = 0  # the background stays black whatever the palette
+        Image.fromarray(palette[sk_map]).save(save_path[:-len("_mask.png")] + "_skeleton.png")
     return save_path
 
 
@@ -267,7 +297,8 @@ def predict(args):
     t0 = time_synchronized()
     saved = [detect_image(f, model, num_classes, exp_folder, mix_type=args.mix_type, device=device, tile=args.tile,
                           overlap=args.overlap, tile_batch=args.tile_batch, bf16=args.bf16, min_area=args.min_area,
-                          max_hole=args.max_hole, connectivity=args.connectivity, components=args.components)
+                          max_hole=args.max_hole, connectivity=args.connectivity, components=args.components,
+                          skeleton=args.skeleton)
              for f in files if f.endswith((".jpg", ".png", ".jpeg"))]
     print(f"inference time for: {time_synchronized() - t0}")
     return saved
@@ -300,6 +331,9 @@ def parse_args(argv=None):
     p.add_argument("--components", action="store_true",
                    help="also write <name>_components.json: class, area and bbox [x0, y0, x1, y1] of every "
                         "component of the cleaned label map")
+    p.add_argument("--skeleton", action="store_true",
+                   help="also write <name>_skeleton.png: the centerlines (Guo-Hall thinning) of the cleaned label map in "
+                        "the class colours on black; with --components the list gains skeleton_px per component")
     return p.parse_args(argv)
 
 

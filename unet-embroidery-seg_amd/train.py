@@ -182,6 +182,8 @@ def train(args):
     mvb = args.max_val_batches or None
     best_score, best_epoch, best_metrics = -1.0, None, None
     best_path, last_path = os.path.join(weights_folder, "best.pth"), os.path.join(weights_folder, "last.pth")
+    # the clDice metric of the validation and test passes (model selection stays on IoU / Mean IoU)
+    skel = {"max_passes": args.skeleton_max_passes} if args.skeleton_metrics else None
     train_losses, val_losses, history = [], [], []
     t0 = time.time()
     for epoch in range(args.epochs):
@@ -210,16 +212,16 @@ def train(args):
         if rank != 0:
             continue
         if args.task == "multitask":
-            metrics = evaluate_multitask(model, val_loader, device, criterion, mvb)
+            metrics = evaluate_multitask(model, val_loader, device, criterion, mvb, skeleton=skel)
             print(f"Val - IoU: {metrics['IoU']:.4f}, Dice: {metrics['Dice']:.4f}, Cls Acc: {metrics['Cls Acc']:.2f}%")
             score = float(metrics["IoU"])
         elif args.task == "binary":
             metrics = evaluate_binary(model, val_loader, device, loss_name=args.loss, pos_weight=pos_weight,
-                                      ignore_index=None, max_batches=mvb, **bnd)
+                                      ignore_index=None, max_batches=mvb, skeleton=skel, **bnd)
             score = float(metrics["IoU"])
         else:
             metrics = evaluate(model, val_loader, device, args.use_dice, args.loss == "focal", num_classes,
-                               lovasz_softmax=args.loss == "lovasz_softmax")
+                               lovasz_softmax=args.loss == "lovasz_softmax", skeleton=skel)
             score = float(metrics["Mean IoU"])
         val_losses.append(metrics["Loss"])
         history.append(metrics)
@@ -245,12 +247,12 @@ def train(args):
             if test_loader is None:
                 pass
             elif args.task == "multitask":
-                test_metrics = evaluate_multitask(model, test_loader, device, criterion, mtest)
+                test_metrics = evaluate_multitask(model, test_loader, device, criterion, mtest, skeleton=skel)
             elif args.task == "multiclass":
-                test_metrics = evaluate(model, test_loader, device, True, False, num_classes)
+                test_metrics = evaluate(model, test_loader, device, True, False, num_classes, skeleton=skel)
             else:
                 test_metrics = evaluate_binary(model, test_loader, device, loss_name=args.loss, pos_weight=pos_weight,
-                                               ignore_index=None, max_batches=mtest, **bnd)
+                                               ignore_index=None, max_batches=mtest, skeleton=skel, **bnd)
             with open(os.path.join(exp_folder, "test_metrics.json"), "w", encoding="utf-8") as f:
                 json.dump(test_metrics, f, ensure_ascii=False, indent=2)
             # fixed-sample visual export of the test split (train.py:476-486; HF datasets only)
@@ -299,6 +301,11 @@ def parse_args(argv=None):
                    help="adds this multiple of the soft-clDice (centerline Dice) loss to the region loss (--task binary "
                         "and multitask; constant over the run)")
     p.add_argument("--cldice-iters", default=3, type=int, help="levels of the soft skeleton (0 .. 64)")
+    p.add_argument("--skeleton-metrics", action="store_true",
+                   help="validation and test also report clDice, Skeleton Precision and Skeleton Recall on hard "
+                        "skeletons (into the metric history); model selection stays on IoU / Mean IoU")
+    p.add_argument("--skeleton-max-passes", default=None, type=int,
+                   help="cap of the thinning passes; default min(H, W) // 2 + 8")
     p.add_argument("--pos-weight", default="auto")
     p.add_argument("--pos-weight-samples", default=80, type=int)
     p.add_argument("--use-dice", action=argparse.BooleanOptionalAction, default=True)
@@ -328,6 +335,8 @@ def parse_args(argv=None):
         p.error("--boundary-loss-weight must be >= 0")
     if args.task == "multiclass" and (args.boundary_loss_weight > 0 or args.boundary_loss_pixels):
         p.error("--boundary-loss-weight / --boundary-loss-pixels apply to --task binary and multitask only")
+    if args.skeleton_max_passes is not None and args.skeleton_max_passes < 0:
+        p.error("--skeleton-max-passes must be >= 0")
     if args.cldice_weight < 0:
         p.error("--cldice-weight must be >= 0")
     if not 0 <= args.cldice_iters <= 64:

@@ -59,18 +59,31 @@ def stats(root):
     return st.view(4, *root.shape)
 
 
-def components(cls, connectivity=8):
+def components(cls, connectivity=8, skeleton=None):
     """int32 [K,7] on the device: (image, class, area, ymin, xmin, ymax, xmax) of every component of a
     non-zero class, ordered by (image, root index).  The compaction is torch (it sizes its result on
-    the host)."""
+    the host).  ``skeleton``: a map of the shape of ``cls`` that is ``cls`` or 0 at every pixel
+    (``skeleton.thin(cls)``); the table is then [K,8], the last column the component's non-zero pixels of it,
+    counted on the device with integer adds."""
     c = _map(cls)
     N, H, W = c.shape
-    st = stats(label(c, connectivity)).view(4, -1)
+    root = label(c, connectivity)
+    st = stats(root).view(4, -1)
     flat = c.view(-1)
     at = torch.nonzero((st[0] > 0) & (flat != 0)).view(-1)  # ascending: (image, root index)
     image, idx = at // (H * W), at % (H * W)
     area, ymax, xmin, xmax = (st[k][at].long() for k in range(4))
-    return torch.stack([image, flat[at].long(), area, idx // W, xmin, ymax, xmax], 1).to(torch.int32)
+    cols = [image, flat[at].long(), area, idx // W, xmin, ymax, xmax]
+    if skeleton is not None:
+        sk = _map(skeleton, "skeleton")
+        if sk.shape != c.shape or sk.device != c.device:
+            raise ValueError(f"skeleton {tuple(sk.shape)} on {sk.device} and cls {tuple(c.shape)} on {c.device} differ")
+        on = torch.nonzero(sk.view(-1) != 0).view(-1)
+        # a pixel's root is an index inside its image: the image's offset makes it one into the flat batch
+        where = on // (H * W) * (H * W) + root.view(-1)[on].long()
+        px = torch.zeros(N * H * W, dtype=torch.int64, device=c.device).index_add_(0, where, torch.ones_like(where))
+        cols.append(px[at])
+    return torch.stack(cols, 1).to(torch.int32)
 
 
 def _filtered(c, connectivity, step, threshold):

@@ -149,6 +149,10 @@ SIGNATURES = {
     "unetseg_soft_skel_bwd": (I, [P, I, I, I, I, P, SZ, P, P, P]),
     "unetseg_cldice_workspace": (SZ, [I, I, I, I]),
     "unetseg_cldice_fwd": (I, [P, I, P, I, I, I, L, I, F, F, P, SZ, P, I, P, P]),
+    "unetseg_skel_tile": (I, [P, P, P]),
+    "unetseg_skel_workspace": (SZ, [I, I, I]),
+    "unetseg_skel_thin": (I, [P, I, I, I, I, P, P, P, SZ, P]),
+    "unetseg_skel_counts": (I, [P, P, P, P, P, P, I, I, I, I, I, P, P]),
 }
 
 #: functions returning a value rather than a status (no RuntimeError on non-zero)

@@ -17,6 +17,7 @@ from torch.amp import autocast
 
 from unetseg_hip import losses
 from unetseg_hip.boundary import Accumulator as BoundaryAccumulator, labels_from_logits
+from unetseg_hip.skeleton import Accumulator as SkeletonAccumulator
 from utils.utils import get_lr
 
 
@@ -167,14 +168,32 @@ def _boundary_acc(boundary, classes=(1,), ignore_index=None):
     return None if boundary is None else BoundaryAccumulator(boundary, classes, ignore_index)
 
 
+def _skeleton_acc(skeleton, classes=(1,), ignore_index=None):
+    """the skeleton-count accumulator (clDice metric) of an evaluation loop, or None without the `skeleton` options"""
+    return None if skeleton is None else SkeletonAccumulator(skeleton, classes, ignore_index)
+
+
+def _add_counts(accs, logits, targets):
+    """one class map of the logits for the accumulators that are on"""
+    accs = [a for a in accs if a is not None]
+    if accs:
+        pred = labels_from_logits(logits)
+        for a in accs:
+            a.add(pred, targets)
+
+
 def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignore_index=None, max_batches=None,
-                    boundary=None, boundary_weight=0.0, boundary_normalize=True, cldice_weight=0.0, cldice_iters=3):
+                    boundary=None, skeleton=None, boundary_weight=0.0, boundary_normalize=True, cldice_weight=0.0,
+                    cldice_iters=3):
     """train_and_eval.py:266-305: eval-mode fp32 forward, global tp/fp/fn/tn, metrics with eps 1e-7.
     boundary_weight, cldice_weight: the training objective's extra terms, so the reported loss is that objective.
     boundary: None, or {"tolerance": px, "biou_d": px or None} to add the boundary metrics of class 1
-    (unetseg_hip/boundary.py), counted on the device and read with the confusion counts."""
+    (unetseg_hip/boundary.py), counted on the device and read with the confusion counts.
+    skeleton: None, or {"max_passes": int or None} to add clDice, Skeleton Precision and Skeleton Recall of class 1
+    on hard skeletons (unetseg_hip/skeleton.py), counted on the device and pooled over the split."""
     model_eval = model.eval().to(device)
     bacc = _boundary_acc(boundary, (1,), ignore_index)
+    sacc = _skeleton_acc(skeleton, (1,), ignore_index)
     total_loss = torch.zeros((), dtype=torch.float64, device=device)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     seen_batches = 0
@@ -186,8 +205,7 @@ def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignor
                                             boundary_normalize, cldice_weight, cldice_iters)
             total_loss += loss
             losses.binary_confusion(outputs, pngs, conf, ignore_index)
-            if bacc is not None:
-                bacc.add(labels_from_logits(outputs), pngs)
+            _add_counts((bacc, sacc), outputs, pngs)
             seen_batches += 1
             if max_batches is not None and seen_batches >= max_batches:
                 break
@@ -196,6 +214,8 @@ def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignor
     metrics["Loss"] = float(total_loss.item() / max(seen_batches, 1))
     if bacc is not None:
         metrics.update(bacc.metrics())
+    if sacc is not None:
+        metrics.update(sacc.metrics())
     return metrics
 
 
@@ -236,12 +256,13 @@ def train_one_epoch_multitask(model, optimizer, train_loader, device, criterion,
     return l, sl, cl, 100.0 * float(correct.item()) / max(total, 1)
 
 
-def evaluate_multitask(model, loader, device, criterion, max_batches=None, boundary=None):
+def evaluate_multitask(model, loader, device, criterion, max_batches=None, boundary=None, skeleton=None):
     """train.py:294-355 / val.py:73-110: eval-mode forward; seg IoU = I/(U+1e-6), Dice = 2I/(|P|+|T|+1e-6)
     with P = sigmoid(seg) > 0.5 (fused confusion kernel, u64 counts on the device); cls accuracy %.
-    boundary: as in evaluate_binary, on the segmentation head."""
+    boundary, skeleton: as in evaluate_binary, on the segmentation head."""
     model.eval()
     bacc = _boundary_acc(boundary)
+    sacc = _skeleton_acc(skeleton)
     sums = torch.zeros(3, dtype=torch.float64, device=device)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     correct = torch.zeros((), dtype=torch.int64, device=device)
@@ -256,8 +277,7 @@ def evaluate_multitask(model, loader, device, criterion, max_batches=None, bound
             loss, seg_loss, cls_loss = criterion(seg_logits, cls_logits, seg_targets, cls_targets)
             sums += torch.stack([loss, seg_loss, cls_loss]).double()
             losses.binary_confusion(seg_logits, seg_targets, conf)
-            if bacc is not None:
-                bacc.add(labels_from_logits(seg_logits), seg_targets)
+            _add_counts((bacc, sacc), seg_logits, seg_targets)
             correct += cls_logits.argmax(1).eq(cls_targets).sum()
             total += cls_targets.size(0)
     tp, fp, fn, _tn = (float(v) for v in conf.tolist())
@@ -269,6 +289,8 @@ def evaluate_multitask(model, loader, device, criterion, max_batches=None, bound
                "Cls Acc": 100.0 * float(correct.item()) / max(total, 1)}
     if bacc is not None:
         metrics.update(bacc.metrics())
+    if sacc is not None:
+        metrics.update(sacc.metrics())
     return metrics
 
 
@@ -349,13 +371,17 @@ def train_one_epoch(model, optimizer, train_loader, device, dice_loss, focal_los
     return float(epoch_loss.item()) / max(n_batches, 1)
 
 
-def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lovasz_softmax=False, boundary=None):
+def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lovasz_softmax=False, boundary=None,
+             skeleton=None):
     """train_and_eval.py:411-513: per-batch metrics averaged over batches, as the reference does.
     boundary: None, or {"tolerance": px, "biou_d": px or None} to add the boundary metrics: counted over
     the split per class 1 .. num_classes - 1 with num_classes as the ignored target value, each key the
-    mean over the classes with a target edge pixel (0.0 without one)."""
+    mean over the classes with a target edge pixel (0.0 without one).
+    skeleton: None, or {"max_passes": int or None} to add the clDice metrics in the same way: the mean over the
+    classes whose target skeleton is non-empty in the split."""
     import numpy as np
     bacc = _boundary_acc(boundary, tuple(range(1, num_classes)), num_classes)
+    sacc = _skeleton_acc(skeleton, tuple(range(1, num_classes)), num_classes)
     weights = torch.tensor(np.ones([num_classes], np.float32)).to(device)
     model_eval = model.eval().to(device)
     hists, loss_sum = [], torch.zeros((), dtype=torch.float64, device=device)
@@ -366,8 +392,7 @@ def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lova
             loss_sum += _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss,
                                  lovasz_softmax).double()
             hists.append(losses.mc_confusion(outputs, pngs))
-            if bacc is not None:
-                bacc.add(labels_from_logits(outputs), pngs)
+            _add_counts((bacc, sacc), outputs, pngs)
     n = max(len(val_loader), 1)
     keys = ("Pixel Accuracy", "Mean Accuracy", "Mean IoU", "Frequency Weighted IoU")
     tot = dict.fromkeys(keys, 0.0)
@@ -379,4 +404,6 @@ def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lova
     metrics["Loss"] = float(loss_sum.item()) / n
     if bacc is not None:
         metrics.update(bacc.metrics())
+    if sacc is not None:
+        metrics.update(sacc.metrics())
     return metrics

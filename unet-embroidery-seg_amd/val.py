@@ -9,6 +9,8 @@ synthetic test split (`--data-path synthetic`, binary / multitask only).
 
 `--boundary-metrics` adds boundary precision / recall / F1 at `--boundary-tolerance` pixels, Boundary
 IoU at `--boundary-iou-d` pixels and HD95 (unetseg_hip/boundary.py), printed after the usual lines.
+`--skeleton-metrics` adds clDice, Skeleton Precision and Skeleton Recall on hard skeletons
+(unetseg_hip/skeleton.py; `--skeleton-max-passes` caps the thinning passes), printed after those.
 
 `--tta MODE` evaluates the model under flip / quarter-turn test-time augmentation
 (unetseg_hip/tta.py): the metrics and the reported loss are then computed on the merged
@@ -31,6 +33,7 @@ from model.model_factory import SUPPORTED_MODELS, build_model  # noqa: E402
 from unetseg_hip import losses  # noqa: E402
 from unetseg_hip.boundary import KEYS as BOUNDARY_KEYS, Accumulator as BoundaryAccumulator  # noqa: E402
 from unetseg_hip.boundary import labels_from_logits  # noqa: E402
+from unetseg_hip.skeleton import KEYS as SKELETON_KEYS, Accumulator as SkeletonAccumulator  # noqa: E402
 from unetseg_hip.tta import MODES as TTA_MODES, TTA  # noqa: E402
 from utils.hf_dataloader import DeviceLoader, HFUnetDataset, make_collate  # noqa: E402
 from utils.synthetic import SyntheticSegDataset, collate  # noqa: E402
@@ -51,8 +54,21 @@ def print_boundary(m):
     print("\t".join(f"{m[k]:.4f}" for k in BOUNDARY_KEYS))
 
 
+def skeleton_options(args):
+    """the `skeleton` argument of the evaluate loops from the flags; None without --skeleton-metrics"""
+    if not args.skeleton_metrics:
+        return None
+    return {"max_passes": args.skeleton_max_passes}
+
+
+def print_skeleton(m):
+    print("\t".join(f"{LogColor.RED}{k}{LogColor.RESET}" for k in SKELETON_KEYS))
+    print("\t".join(f"{m[k]:.4f}" for k in SKELETON_KEYS))
+
+
 def val(args):
     boundary = boundary_options(args)
+    skeleton = skeleton_options(args)
     num_classes = args.num_classes + 1 if args.task == "multiclass" else 2  # val.py:22-27
     device = torch.device(args.device)
     input_shape = [args.input_size] * 2
@@ -83,23 +99,28 @@ def val(args):
         m = evaluate_binary(model, loader, device, loss_name=args.loss, pos_weight=None, ignore_index=None,
                             boundary=boundary, boundary_weight=args.boundary_loss_weight,
                             boundary_normalize=not args.boundary_loss_pixels, cldice_weight=args.cldice_weight,
-                            cldice_iters=args.cldice_iters)
+                            cldice_iters=args.cldice_iters, skeleton=skeleton)
         print(f"{LogColor.RED}Dice{LogColor.RESET}\t{LogColor.RED}IoU{LogColor.RESET}\t{LogColor.RED}Precision"
               f"{LogColor.RESET}\t{LogColor.RED}Recall{LogColor.RESET}\t{LogColor.RED}Accuracy{LogColor.RESET}")
         print(f"{m['Dice']:.4f}\t{m['IoU']:.4f}\t{m['Precision']:.4f}\t{m['Recall']:.4f}\t{m['Accuracy']:.4f}")
         if boundary is not None:
             print_boundary(m)
+        if skeleton is not None:
+            print_skeleton(m)
         return m
     if args.task == "multiclass":
         m = evaluate(model, loader, device, dice_loss=True, focal_loss=False, num_classes=num_classes,
-                     lovasz_softmax=args.loss == "lovasz_softmax", boundary=boundary)
-        print({k: v for k, v in m.items() if k not in BOUNDARY_KEYS})
+                     lovasz_softmax=args.loss == "lovasz_softmax", boundary=boundary, skeleton=skeleton)
+        print({k: v for k, v in m.items() if k not in BOUNDARY_KEYS and k not in SKELETON_KEYS})
         if boundary is not None:
             print_boundary(m)
+        if skeleton is not None:
+            print_skeleton(m)
         return m
 
     model.eval()
     bacc = None if boundary is None else BoundaryAccumulator(boundary)
+    sacc = None if skeleton is None else SkeletonAccumulator(skeleton)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     per_cls = torch.zeros(3, 2, dtype=torch.int64, device=device)  # [class][correct, count]
     with torch.no_grad():
@@ -107,8 +128,11 @@ def val(args):
             images, seg_t, cls_t = images.to(device), seg_t.to(device), cls_t.to(device)
             seg_logits, cls_logits = model(images)
             losses.binary_confusion(seg_logits, seg_t, conf)
-            if bacc is not None:
-                bacc.add(labels_from_logits(seg_logits), seg_t)
+            if bacc is not None or sacc is not None:
+                seg_pred = labels_from_logits(seg_logits)
+                for acc_ in (bacc, sacc):
+                    if acc_ is not None:
+                        acc_.add(seg_pred, seg_t)
             pred = cls_logits.argmax(1)
             for c in range(3):
                 sel = cls_t == c
@@ -130,6 +154,9 @@ def val(args):
     if bacc is not None:
         m.update(bacc.metrics())
         print_boundary(m)
+    if sacc is not None:
+        m.update(sacc.metrics())
+        print_skeleton(m)
     return m
 
 
@@ -162,6 +189,12 @@ def parse_args(argv=None):
                    help="pixel tolerance of boundary precision / recall / F1")
     p.add_argument("--boundary-iou-d", default=0, type=int,
                    help="Boundary-IoU band width in pixels; 0 = 2 %% of the image diagonal")
+    p.add_argument("--skeleton-metrics", action="store_true",
+                   help="also report clDice, Skeleton Precision and Skeleton Recall on hard (thinned) skeletons (class "
+                        "1; multiclass: the mean over the classes with a target skeleton)")
+    p.add_argument("--skeleton-max-passes", default=None, type=int,
+                   help="cap of the thinning passes; default min(H, W) // 2 + 8.  An image still losing pixels at the "
+                        "cap is an error, not a silently wrong score")
     p.add_argument("--boundary-loss-weight", default=0.0, type=float,
                    help="the training run's boundary-loss weight, so the reported loss (m['Loss'], --task binary) is "
                         "that objective; the multitask evaluation reports no loss")
@@ -171,6 +204,8 @@ def parse_args(argv=None):
                    help="the training run's soft-clDice weight, so the reported loss (--task binary) is that objective")
     p.add_argument("--cldice-iters", default=3, type=int, help="levels of the soft skeleton (0 .. 64)")
     args = p.parse_args(argv)
+    if args.skeleton_max_passes is not None and args.skeleton_max_passes < 0:
+        p.error("--skeleton-max-passes must be >= 0")
     if args.cldice_weight < 0:
         p.error("--cldice-weight must be >= 0")
     if not 0 <= args.cldice_iters <= 64:
