@@ -37,16 +37,17 @@ def _need_gpu():
     load()
 
 
-def _guarded(n, dtype, fill, init=None):
-    buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device=DEV)
-    view = buf[GUARD:GUARD + n]
+def _guarded(n, dtype, fill, init=None, shift=0):
+    """(buffer, view of n elements starting GUARD + shift elements in): the buffer is `fill` outside the view"""
+    buf = torch.full((n + 2 * GUARD + shift,), fill, dtype=dtype, device=DEV)
+    view = buf[GUARD + shift:GUARD + shift + n]
     if init is not None:
         view.copy_((init if isinstance(init, torch.Tensor) else torch.tensor(init)).reshape(-1))
     return buf, view
 
 
-def _intact(buf, n, fill):
-    head, tail = buf[:GUARD], buf[GUARD + n:]
+def _intact(buf, n, fill, shift=0):
+    head, tail = buf[:GUARD + shift], buf[GUARD + shift + n:]
     if isinstance(fill, float) and math.isnan(fill):
         return bool(torch.isnan(head).all()) and bool(torch.isnan(tail).all())
     return bool((head == fill).all()) and bool((tail == fill).all())
@@ -128,13 +129,14 @@ def test_soft_skeleton_function(form):
         losses.soft_skeleton(x.detach(), iters=65)
 
 
-def _run_loss(case, weight=WEIGHT, accumulate=0, gz_init=None, want_gz=True):
+def _run_loss(case, weight=WEIGHT, accumulate=0, gz_init=None, want_gz=True, shift=0):
+    """shift: elements by which out, tgt and gz are moved off their 16-byte alignment"""
     from unetseg_hip.lib import lib
     B, H, W = case["shape"]
     n, nch, k = B * H * W, case["nch"], case["iters"]
-    obuf, out = _guarded(n * nch, torch.float32, 7.5, case["out"])
-    tbuf, tgt = _guarded(n, torch.int64, 1, case["t"])
-    gbuf, gz = _guarded(n, torch.float32, NAN, gz_init if gz_init is not None else torch.full((n,), NAN))
+    obuf, out = _guarded(n * nch, torch.float32, 7.5, case["out"], shift)
+    tbuf, tgt = _guarded(n, torch.int64, 1, case["t"], shift)
+    gbuf, gz = _guarded(n, torch.float32, NAN, gz_init if gz_init is not None else torch.full((n,), NAN), shift)
     nb = lib.cldice_workspace(B, H, W, k)
     wbuf = torch.full((nb + 512,), 0xA5, dtype=torch.uint8, device=DEV)
     lbuf = torch.full((3,), NAN, dtype=torch.float32, device=DEV)
@@ -142,8 +144,8 @@ def _run_loss(case, weight=WEIGHT, accumulate=0, gz_init=None, want_gz=True):
                    float(weight), wbuf.data_ptr() + 256, nb, gz.data_ptr() if want_gz else None, accumulate,
                    lbuf.data_ptr() + 4, _stream())
     torch.cuda.synchronize()
-    assert _intact(gbuf, n, NAN), "write outside gz"
-    assert _intact(obuf, n * nch, 7.5) and _intact(tbuf, n, 1)
+    assert _intact(gbuf, n, NAN, shift), "write outside gz"
+    assert _intact(obuf, n * nch, 7.5, shift) and _intact(tbuf, n, 1, shift)
     assert bool((wbuf[:256] == 0xA5).all()) and bool((wbuf[256 + nb:] == 0xA5).all()), "write outside the workspace"
     assert math.isnan(lbuf[0].item()) and math.isnan(lbuf[2].item())
     assert torch.equal(out.cpu(), torch.tensor(case["out"]).reshape(-1)), "logits changed"
@@ -186,6 +188,17 @@ def test_accumulate_and_repeat(case):
     _, gza = _run_loss(c, accumulate=1, gz_init=g0)
     want = (g0 + torch.from_numpy(gz).reshape(-1)).numpy().reshape(gz.shape)  # the product, then the sum
     assert gza.tobytes() == want.tobytes()
+
+
+@pytest.mark.parametrize("nch", [1, 2])
+def test_unaligned_pointers(nch):
+    """out, tgt and gz one element off their 16-byte alignment take the element loads and stores: same bits.
+    2574 pixels leave a tail group, and 858 per image put groups across two images"""
+    c = C.loss_case((3, 13, 66), nch, True, 3, "mixed")
+    a = _run_loss(c)
+    b = _run_loss(c, shift=1)
+    assert np.float32(a[0]).tobytes() == np.float32(b[0]).tobytes()
+    assert a[1].tobytes() == b[1].tobytes()
 
 
 @pytest.mark.parametrize("form", ["B2HW", "B1HW", "BHW"])

@@ -32,47 +32,11 @@
 // e = expf(-|z|), d = 1 + e, hi = 1 / d = sigmoid(|z|), lo = e / d = sigmoid(-|z|): p = hi or lo by the
 // sign of z, and p (1 - p) = hi * lo, which keeps its relative accuracy where 1 - p would cancel.
 #include "boundary_edt.h"
-#include "elem_util.h"
+#include "seg_pixel.h"
 
 namespace {
 
 constexpr int kBlGrid = 2048;  // block cap of the sites and loss kernels (their partial buffers are sized by it)
-
-typedef long i64x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// v = p[0 .. 3]: 16-byte loads when p is 16-byte aligned (the same for every group of an array whose
-// base is, as groups start at multiples of 4 elements), else element loads
-__device__ __forceinline__ void ld4(const int64_t* p, long (&v)[4]) {
-  if (aligned16(p)) {
-    const i64x2 a = *reinterpret_cast<const i64x2*>(p), b = *reinterpret_cast<const i64x2*>(p + 2);
-    v[0] = a.x, v[1] = a.y, v[2] = b.x, v[3] = b.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = p[k];
-  }
-}
-template <typename T>  // a 4-byte T
-__device__ __forceinline__ void ld4(const T* p, T (&v)[4]) {
-  if (aligned16(p)) {
-    const uint4 raw = *reinterpret_cast<const uint4*>(p);
-    const T* e = reinterpret_cast<const T*>(&raw);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = e[k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = p[k];
-  }
-}
-__device__ __forceinline__ void st4(float* p, const float (&v)[4]) {
-  if (aligned16(p)) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) p[k] = v[k];
-  }
-}
 
 // ---- 1. site maps ------------------------------------------------------------------------------------
 // thread = 4 consecutive pixels of the flat batch; fg / bg uint8 [total]; cnt[block] = valid pixels seen
@@ -86,11 +50,7 @@ __global__ __launch_bounds__(256) void bl_sites_kernel(const int64_t* tgt, long 
     const long i0 = g * 4;
     const int m = total - i0 < 4 ? (int)(total - i0) : 4;  // pixels of the group inside the batch
     long t[4] = {0, 0, 0, 0};
-    if (m == 4) {
-      ld4(tgt + i0, t);
-    } else {
-      for (int k = 0; k < m; ++k) t[k] = tgt[i0 + k];
-    }
+    ld_group(tgt + i0, m, t);
     unsigned f = 0, b = 0;  // the group's site bytes, pixel k in byte k
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -118,9 +78,7 @@ __global__ __launch_bounds__(256) void bl_sites_kernel(const int64_t* tgt, long 
 __global__ __launch_bounds__(256) void bl_count_kernel(const unsigned* cnt, int G, float inv_norm, double* nvalid,
                                                        float* scale) {
   __shared__ unsigned long long sred[16];
-  unsigned long long n = 0;
-  for (int i = threadIdx.x; i < G; i += 256) n += cnt[i];
-  n = block_sum(n, sred);
+  const unsigned long long n = sum_parts(cnt, G, sred);
   if (threadIdx.x == 0) {
     nvalid[0] = (double)n;
     scale[0] = n > 0 ? (float)((double)inv_norm / (double)n) : 0.f;
@@ -128,13 +86,6 @@ __global__ __launch_bounds__(256) void bl_count_kernel(const unsigned* cnt, int 
 }
 
 // ---- 4. the loss pass ------------------------------------------------------------------------------------
-// z of pixel px of image b of planar fp32 logits [B][nch][P]
-__device__ __forceinline__ float bl_z(const float* out, int nch, long P, long b, long px) {
-  const float* base = out + b * nch * P + px;
-  const float o0 = base[0], o1 = base[nch == 2 ? P : 0];
-  return nch == 2 ? o1 - o0 : o0;
-}
-
 // thread = 4 consecutive pixels of the flat batch.  d2fg / d2bg int32 [total]; gz, phi fp32 [total] (either
 // may be NULL); part[block] = the block's sum of p * phi over its valid pixels
 __global__ __launch_bounds__(256) void bl_loss_kernel(const float* out, int nch, long P, const int64_t* tgt,
@@ -155,31 +106,11 @@ __global__ __launch_bounds__(256) void bl_loss_kernel(const float* out, int nch,
     long t[4] = {0, 0, 0, 0};
     int df[4] = {0, 0, 0, 0}, db[4] = {0, 0, 0, 0};
     float z[4] = {0.f, 0.f, 0.f, 0.f}, acc[4] = {0.f, 0.f, 0.f, 0.f};
-    const long b0 = i0 / P, px0 = i0 - b0 * P;
-    if (m == 4) {
-      ld4(tgt + i0, t);
-      ld4(d2fg + i0, df);
-      ld4(d2bg + i0, db);
-      if (accumulate && gz) ld4(gz + i0, acc);
-    } else {
-      for (int k = 0; k < m; ++k) {
-        t[k] = tgt[i0 + k], df[k] = d2fg[i0 + k], db[k] = d2bg[i0 + k];
-        if (accumulate && gz) acc[k] = gz[i0 + k];
-      }
-    }
-    if (m == 4 && px0 + 4 <= P) {  // the group lies in one image: its logit planes are contiguous
-      const float* base = out + b0 * nch * P + px0;
-      float o0[4], o1[4];
-      ld4(base, o0);
-      ld4(base + (nch == 2 ? P : 0), o1);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) z[k] = nch == 2 ? o1[k] - o0[k] : o0[k];
-    } else {
-      for (int k = 0; k < m; ++k) {
-        const long i = i0 + k, b = i / P;
-        z[k] = bl_z(out, nch, P, b, i - b * P);
-      }
-    }
+    ld_group(tgt + i0, m, t);
+    ld_group(d2fg + i0, m, df);
+    ld_group(d2bg + i0, m, db);
+    if (accumulate && gz) ld_group(gz + i0, m, acc);
+    ld_logit_group(out, nch, P, i0, m, z);
     float f[4], v[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -187,22 +118,13 @@ __global__ __launch_bounds__(256) void bl_loss_kernel(const float* out, int nch,
       const int d2 = isfg ? db[k] : df[k];
       const float r = (float)sqrt((double)d2);  // one rounding: the double root of an integer, cast
       f[k] = !valid || d2 == kEdtInf ? 0.f : (isfg ? 1.f - r : r);  // r >= 1 on fg; r - 1 is exact
-      const float e = expf(-fabsf(z[k]));
-      const float d = 1.f + e, hi = 1.f / d, lo = e / d;
-      const float p = z[k] >= 0.f ? hi : lo;
-      const float term = valid ? ((hi * lo) * f[k]) * sc : 0.f;
+      const Sigmoid sg = sigmoid_parts(z[k]);
+      const float term = valid ? ((sg.hi * sg.lo) * f[k]) * sc : 0.f;
       v[k] = acc[k] + weight * term;
-      if (valid) s += (double)p * (double)f[k];
+      if (valid) s += (double)sg.p * (double)f[k];
     }
-    if (m == 4) {
-      if (gz) st4(gz + i0, v);
-      if (phi) st4(phi + i0, f);
-    } else {
-      for (int k = 0; k < m; ++k) {
-        if (gz) gz[i0 + k] = v[k];
-        if (phi) phi[i0 + k] = f[k];
-      }
-    }
+    if (gz) st_group(gz + i0, m, v);
+    if (phi) st_group(phi + i0, m, f);
   }
   s = block_sum(s, sred);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
@@ -212,13 +134,9 @@ __global__ __launch_bounds__(256) void bl_loss_kernel(const float* out, int nch,
 __global__ __launch_bounds__(256) void bl_final_kernel(const double* part, int G, const double* nvalid,
                                                        float inv_norm, float* loss) {
   __shared__ double sred[16];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < G; i += 256) s += part[i];
-  s = block_sum(s, sred);
+  const double s = sum_parts(part, G, sred);
   if (threadIdx.x == 0) loss[0] = nvalid[0] > 0.0 ? (float)(s * (double)inv_norm / nvalid[0]) : 0.f;
 }
-
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // the workspace: sites uint8 [2][total] | d2 int32 [2][total] | cnt [kBlGrid] | part [kBlGrid], nvalid | scale
 struct BlWorkspace {

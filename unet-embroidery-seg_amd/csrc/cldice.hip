@@ -39,7 +39,7 @@
 //               dL/dtsens / (sum S(y) + smooth)) in device scalars
 //   4. backward of S(p) from gs_k = cA (y - tprec), formed in the level-k kernel
 //   5. gz:      gz (+)= weight * ((Gx_0 + cB S(y)) * p (1 - p))
-#include "elem_util.h"
+#include "seg_pixel.h"
 
 namespace {
 
@@ -47,36 +47,7 @@ constexpr int kT = 32;         // tile edge
 constexpr int kCdGrid = 2048;  // block cap of the elementwise passes (their partial buffers are sized by it)
 constexpr int kMaxIters = 64;
 
-__device__ __forceinline__ bool cd_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-typedef long cd_i64x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void cd_ld4(const int64_t* p, long (&v)[4]) {
-  if (cd_aligned16(p)) {
-    const cd_i64x2 a = *reinterpret_cast<const cd_i64x2*>(p), b = *reinterpret_cast<const cd_i64x2*>(p + 2);
-    v[0] = a.x, v[1] = a.y, v[2] = b.x, v[3] = b.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = p[k];
-  }
-}
-__device__ __forceinline__ void cd_ld4(const float* p, float (&v)[4]) {
-  if (cd_aligned16(p)) {
-    const float4 a = *reinterpret_cast<const float4*>(p);
-    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = p[k];
-  }
-}
-__device__ __forceinline__ void cd_st4(float* p, const float (&v)[4]) {
-  if (cd_aligned16(p)) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) p[k] = v[k];
-  }
-}
+using Tiles = TileGrid<kT>;
 
 // ---- stencil pieces on an LDS region ---------------------------------------------------------------------
 // a[] has row pitch `pitch`; i is the centre's index.  Pixels outside the image hold +inf for a min window and
@@ -109,22 +80,6 @@ __device__ __forceinline__ float box_max(const float* a, int i, int pitch, int& 
   return best;
 }
 
-// block -> (image, tile origin)
-struct TilePos {
-  long img;
-  int y0, x0;
-};
-__device__ __forceinline__ TilePos tile_pos(int tiles_x, int tiles_y) {
-  const long b = blockIdx.x;
-  const long per = (long)tiles_x * tiles_y;
-  TilePos t;
-  t.img = b / per;
-  const int r = (int)(b - t.img * per);
-  t.y0 = (r / tiles_x) * kT;
-  t.x0 = (r % tiles_x) * kT;
-  return t;
-}
-
 // region of edge kT + 2 * halo around the tile <- src (one image), `outside` where the image ends
 template <int HALO>
 __device__ __forceinline__ void stage(const float* src, int H, int W, int y0, int x0, float outside, float* dst) {
@@ -147,7 +102,7 @@ __global__ __launch_bounds__(256) void skel_fwd_kernel(const float* xin, const f
   __shared__ float X0[FIRST ? 1 : R3 * R3];  // x_{j-1}, tile + 3, +inf outside
   __shared__ float X1[R2 * R2];              // x_j,     tile + 2, +inf outside
   __shared__ float E1[R1 * R1];              // E(x_j),  tile + 1, -inf outside
-  const TilePos tp = tile_pos(tiles_x, tiles_y);
+  const Tiles::Pos tp = Tiles::pos(tiles_x, tiles_y);
   const long base = tp.img * H * W;
   const float inf = __builtin_inff();
   if (FIRST) {
@@ -202,7 +157,7 @@ __global__ __launch_bounds__(256) void skel_bwd_kernel(const float* xj, const fl
   __shared__ float GU[R2 * R2];         // gu,       tile + 2, 0 outside
   __shared__ unsigned char Amax[R2 * R2];  // D's winner at that pixel, 255 outside
   __shared__ float GE[R1 * R1];         // ge,       tile + 1, 0 outside
-  const TilePos tp = tile_pos(tiles_x, tiles_y);
+  const Tiles::Pos tp = Tiles::pos(tiles_x, tiles_y);
   const long base = tp.img * H * W;
   const float inf = __builtin_inff();
   stage<4>(xj + base, H, W, tp.y0, tp.x0, inf, X);
@@ -283,43 +238,20 @@ __global__ __launch_bounds__(256) void cd_maps_kernel(const float* out, int nch,
     const int m = total - i0 < 4 ? (int)(total - i0) : 4;
     long t[4] = {0, 0, 0, 0};
     float z[4] = {0.f, 0.f, 0.f, 0.f};
-    const long b0 = i0 / P, px0 = i0 - b0 * P;
-    if (m == 4) {
-      cd_ld4(tgt + i0, t);
-    } else {
-      for (int k = 0; k < m; ++k) t[k] = tgt[i0 + k];
-    }
-    if (m == 4 && px0 + 4 <= P) {  // the group lies in one image: its logit planes are contiguous
-      const float* base = out + b0 * nch * P + px0;
-      float o0[4], o1[4];
-      cd_ld4(base, o0);
-      cd_ld4(base + (nch == 2 ? P : 0), o1);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) z[k] = nch == 2 ? o1[k] - o0[k] : o0[k];
-    } else {
-      for (int k = 0; k < m; ++k) {
-        const long i = i0 + k, b = i / P;
-        const float* base = out + b * nch * P + (i - b * P);
-        z[k] = nch == 2 ? base[P] - base[0] : base[0];
-      }
-    }
+    ld_group(tgt + i0, m, t);
+    ld_logit_group(out, nch, P, i0, m, z);
     float pv[4], yv[4], hv[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const bool valid = !(has_ign && t[k] == ignore);
-      const float e = expf(-fabsf(z[k]));
-      const float d = 1.f + e, hi = 1.f / d, lo = e / d;
-      pv[k] = valid ? (z[k] >= 0.f ? hi : lo) : 0.f;
+      const Sigmoid sg = sigmoid_parts(z[k]);
+      pv[k] = valid ? sg.p : 0.f;
       yv[k] = valid && t[k] == 1 ? 1.f : 0.f;
-      hv[k] = valid ? hi * lo : 0.f;
+      hv[k] = valid ? sg.hi * sg.lo : 0.f;
     }
-    if (m == 4) {
-      cd_st4(p + i0, pv);
-      cd_st4(y + i0, yv);
-      cd_st4(hl + i0, hv);
-    } else {
-      for (int k = 0; k < m; ++k) p[i0 + k] = pv[k], y[i0 + k] = yv[k], hl[i0 + k] = hv[k];
-    }
+    st_group(p + i0, m, pv);
+    st_group(y + i0, m, yv);
+    st_group(hl + i0, m, hv);
   }
 }
 
@@ -334,11 +266,7 @@ __global__ __launch_bounds__(256) void cd_sums_kernel(const float* sp, const flo
     const int m = total - i0 < 4 ? (int)(total - i0) : 4;
     float vsp[4] = {0.f, 0.f, 0.f, 0.f}, vsy[4] = {0.f, 0.f, 0.f, 0.f}, vp[4] = {0.f, 0.f, 0.f, 0.f},
           vy[4] = {0.f, 0.f, 0.f, 0.f};
-    if (m == 4) {
-      cd_ld4(sp + i0, vsp), cd_ld4(sy + i0, vsy), cd_ld4(p + i0, vp), cd_ld4(y + i0, vy);
-    } else {
-      for (int k = 0; k < m; ++k) vsp[k] = sp[i0 + k], vsy[k] = sy[i0 + k], vp[k] = p[i0 + k], vy[k] = y[i0 + k];
-    }
+    ld_group(sp + i0, m, vsp), ld_group(sy + i0, m, vsy), ld_group(p + i0, m, vp), ld_group(y + i0, m, vy);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       a1 += (double)vsp[k] * (double)vy[k];
@@ -364,11 +292,7 @@ __global__ __launch_bounds__(256) void cd_final_kernel(const double* part, int G
                                                        float* loss) {
   __shared__ double sred[16];
   double s[4];
-  for (int a = 0; a < 4; ++a) {
-    double v = 0.0;
-    for (int i = threadIdx.x; i < G; i += 256) v += part[a * kCdGrid + i];
-    s[a] = block_sum(v, sred);
-  }
+  for (int a = 0; a < 4; ++a) s[a] = sum_parts(part + a * kCdGrid, G, sred);
   if (threadIdx.x == 0) {
     const double sm = (double)smooth;
     const double tp = (s[0] + sm) / (s[1] + sm), ts = (s[2] + sm) / (s[3] + sm), den = tp + ts;
@@ -392,48 +316,29 @@ __global__ __launch_bounds__(256) void cd_gz_kernel(const float* gx0, const floa
     const int m = total - i0 < 4 ? (int)(total - i0) : 4;
     float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f}, h[4] = {0.f, 0.f, 0.f, 0.f},
           acc[4] = {0.f, 0.f, 0.f, 0.f}, v[4];
-    if (m == 4) {
-      cd_ld4(gx0 + i0, a), cd_ld4(sy + i0, b), cd_ld4(hl + i0, h);
-      if (accumulate) cd_ld4(gz + i0, acc);
-    } else {
-      for (int k = 0; k < m; ++k) {
-        a[k] = gx0[i0 + k], b[k] = sy[i0 + k], h[k] = hl[i0 + k];
-        if (accumulate) acc[k] = gz[i0 + k];
-      }
-    }
+    ld_group(gx0 + i0, m, a), ld_group(sy + i0, m, b), ld_group(hl + i0, m, h);
+    if (accumulate) ld_group(gz + i0, m, acc);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float term = h[k] != 0.f ? (a[k] + cB * b[k]) * h[k] : 0.f;
       v[k] = acc[k] + weight * term;
     }
-    if (m == 4) {
-      cd_st4(gz + i0, v);
-    } else {
-      for (int k = 0; k < m; ++k) gz[i0 + k] = v[k];
-    }
+    st_group(gz + i0, m, v);
   }
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------
-inline size_t cd_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the skeleton's workspace, in maps of `map` bytes: x_1 .. x_k | s_0 .. s_{k-1} | gs a, b | Gx a, b
 struct SkelWorkspace {
   size_t map, bytes;
   int k;
   SkelWorkspace(size_t total, int iters) : k(iters) {
-    map = cd_up256(total * sizeof(float));
+    map = up256(total * sizeof(float));
     bytes = map * (2 * (size_t)k + 4);
   }
   float* x(void* ws, int j) const { return (float*)((uint8_t*)ws + map * (size_t)(j - 1)); }      // j = 1 .. k
   float* s(void* ws, int j) const { return (float*)((uint8_t*)ws + map * (size_t)(k + j)); }      // j = 0 .. k-1
   float* scratch(void* ws, int i) const { return (float*)((uint8_t*)ws + map * (size_t)(2 * k + i)); }  // 0 .. 3
-};
-
-struct Tiles {
-  int tx, ty;
-  long blocks;
-  Tiles(int N, int H, int W) : tx((W + kT - 1) / kT), ty((H + kT - 1) / kT) { blocks = (long)tx * ty * N; }
 };
 
 // S_k of x0 -> skel.  keep != NULL: x_1 .. x_k and s_0 .. s_{k-1} stay in its workspace for the backward;
@@ -484,17 +389,11 @@ struct CdWorkspace {
   CdWorkspace(size_t total, int iters) : sk(total, iters) {
     skel = 6 * sk.map;
     part = skel + sk.bytes;
-    coef = part + cd_up256(4 * kCdGrid * sizeof(double));
+    coef = part + up256(4 * kCdGrid * sizeof(double));
     bytes = coef + 256;
   }
   float* map(void* ws, int i) const { return (float*)((uint8_t*)ws + sk.map * (size_t)i); }
 };
-
-inline bool cd_shape_ok(int N, int H, int W) {
-  if (N <= 0 || H <= 0 || W <= 0) return false;
-  const Tiles t(N, H, W);
-  return t.blocks <= 0x7fffffffL && (size_t)N * H * W <= ((size_t)1 << 40);
-}
 
 }  // namespace
 
@@ -504,12 +403,12 @@ inline bool cd_shape_ok(int N, int H, int W) {
 
 // host only
 UNETSEG_API size_t unetseg_soft_skel_workspace(int N, int H, int W, int iters) {
-  if (!cd_shape_ok(N, H, W) || iters < 0 || iters > kMaxIters) return 0;
+  if (!Tiles::shape_ok(N, H, W) || iters < 0 || iters > kMaxIters) return 0;
   return SkelWorkspace((size_t)N * H * W, iters).bytes;
 }
 
 #define CD_CHECK_SKEL(name)                                                                                     \
-  US_CHECK_ARG(cd_shape_ok(N, H, W), name ": bad shape N=%d H=%d W=%d", N, H, W);                               \
+  US_CHECK_ARG(Tiles::shape_ok(N, H, W), name ": bad shape N=%d H=%d W=%d", N, H, W);                               \
   US_CHECK_ARG(iters >= 0 && iters <= kMaxIters, name ": iters %d must be 0 .. %d", iters, kMaxIters);          \
   US_CHECK_ARG(ws_bytes >= unetseg_soft_skel_workspace(N, H, W, iters), name ": workspace too small");          \
   US_CHECK_ARG(((uintptr_t)ws & 15) == 0, name ": the workspace must be 16-byte aligned")
@@ -539,7 +438,7 @@ UNETSEG_API int unetseg_soft_skel_bwd(const float* x, int N, int H, int W, int i
 
 // host only
 UNETSEG_API size_t unetseg_cldice_workspace(int B, int H, int W, int iters) {
-  if (!cd_shape_ok(B, H, W) || iters < 0 || iters > kMaxIters) return 0;
+  if (!Tiles::shape_ok(B, H, W) || iters < 0 || iters > kMaxIters) return 0;
   return CdWorkspace((size_t)B * H * W, iters).bytes;
 }
 
@@ -550,7 +449,7 @@ UNETSEG_API int unetseg_cldice_fwd(const float* out, int nch, const int64_t* tgt
                                    int accumulate, float* loss, void* stream) {
   US_CHECK_ARG(out && tgt && ws && loss, "cldice_fwd: null pointer");  // gz may be NULL
   US_CHECK_ARG(nch == 1 || nch == 2, "cldice_fwd: nch %d must be 1 or 2", nch);
-  US_CHECK_ARG(cd_shape_ok(B, H, W), "cldice_fwd: bad shape B=%d H=%d W=%d", B, H, W);
+  US_CHECK_ARG(Tiles::shape_ok(B, H, W), "cldice_fwd: bad shape B=%d H=%d W=%d", B, H, W);
   US_CHECK_ARG(iters >= 0 && iters <= kMaxIters, "cldice_fwd: iters %d must be 0 .. %d", iters, kMaxIters);
   US_CHECK_ARG(smooth > 0.f, "cldice_fwd: smooth %g must be > 0", (double)smooth);
   US_CHECK_ARG(ignore_index != 1, "cldice_fwd: ignore_index is the foreground class 1");

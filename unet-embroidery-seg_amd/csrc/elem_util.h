@@ -1,6 +1,8 @@
 // Shared by the memory-bound translation units (elem, pool, upsample, pointwise, resize, tiles, tta, augment, loss,
-// lovasz_softmax, multiclass, optim, cls_head): the 16-B vector width, the dtype dispatch and the small host
-// helpers of their C-ABI sections.
+// lovasz_softmax, multiclass, optim, cls_head, ccl, boundary): the 16-B vector width, the dtype dispatch and the
+// small host helpers of their C-ABI sections.  boundary_loss, cldice and skeleton take it through seg_pixel.h,
+// which adds what their per-pixel passes share (four-pixel group loads and stores, the logit group load, the
+// sigmoid pieces, the sum of block partials, the workspace rounding, the tile grid and its shape check).
 #pragma once
 #include <type_traits>
 #include <utility>

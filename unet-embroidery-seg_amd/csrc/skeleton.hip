@@ -46,7 +46,7 @@
 //
 // Everything is integer and every decision is taken from values that do not depend on the order of the
 // blocks, so the result is bitwise reproducible.
-#include "elem_util.h"
+#include "seg_pixel.h"
 
 namespace {
 
@@ -65,29 +65,17 @@ static_assert(kHalo % 4 == 0 && kTW % 4 == 0 && kPitch % 4 == 0, "a four-pixel g
 
 #define SKEL_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-inline size_t skel_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the workspace: map A | map B (bytes, each rounded up to 256) | flags int32 [4][N]
 struct SkelLayout {
   size_t map, flags, bytes;
   SkelLayout(size_t total, int N) {
-    map = skel_up256(total);
+    map = up256(total);
     flags = 2 * map;
-    bytes = flags + skel_up256(4 * (size_t)N * sizeof(int));
+    bytes = flags + up256(4 * (size_t)N * sizeof(int));
   }
 };
 
-struct SkelTiles {
-  int tx, ty;
-  long blocks;
-  SkelTiles(int N, int H, int W) : tx((W + kTW - 1) / kTW), ty((H + kTH - 1) / kTH) { blocks = (long)tx * ty * N; }
-};
-
-inline bool skel_shape_ok(int N, int H, int W) {
-  if (N <= 0 || H <= 0 || W <= 0) return false;
-  const SkelTiles t(N, H, W);
-  return t.blocks <= 0x7fffffffL && (size_t)N * H * W <= ((size_t)1 << 40);
-}
+using SkelTiles = TileGrid<kTW, kTH>;
 
 // ---- pack / finish ----------------------------------------------------------------------------------
 // thread = four consecutive pixels of the flat batch; map is 4-byte aligned and padded to a multiple of 4
@@ -169,13 +157,12 @@ __global__ __launch_bounds__(256) void skel_thin_kernel(const uint8_t* src, uint
   __shared__ uint32_t S0[kLdsWords];
   __shared__ uint32_t S1[kLdsWords];
   __shared__ unsigned chg[kK];
-  const long per = (long)tiles_x * tiles_y;
-  const long img = blockIdx.x / per;
-  const int tile = (int)(blockIdx.x - img * per);
+  const SkelTiles::Pos tp = SkelTiles::pos(tiles_x, tiles_y);
+  const long img = tp.img;
+  const int y0 = tp.y0, x0 = tp.x0;
   // the next launch sets this slot; nothing reads or sets it in this launch
-  if (tile == 0 && threadIdx.x == 0) next[img] = 0;
+  if (tp.tile == 0 && threadIdx.x == 0) next[img] = 0;
   if (prev && __hip_atomic_load(prev + img, SKEL_RLX_AGENT) == 0) return;  // converged: both maps hold the result
-  const int y0 = (tile / tiles_x) * kTH, x0 = (tile % tiles_x) * kTW;
   const long base = img * H * W;
   const bool words = W % 4 == 0;  // then every row starts on a word of the map, and a word is inside the image or outside
   for (int i = threadIdx.x; i < kLdsWords; i += 256) S0[i] = 0, S1[i] = 0;
@@ -304,7 +291,7 @@ UNETSEG_API int unetseg_skel_tile(int* tw, int* th, int* passes_per_launch) {
 
 // host only; 0 for a shape it refuses
 UNETSEG_API size_t unetseg_skel_workspace(int N, int H, int W) {
-  if (!skel_shape_ok(N, H, W)) return 0;
+  if (!SkelTiles::shape_ok(N, H, W)) return 0;
   return SkelLayout((size_t)N * H * W, N).bytes;
 }
 
@@ -313,7 +300,7 @@ UNETSEG_API size_t unetseg_skel_workspace(int N, int H, int W) {
 UNETSEG_API int unetseg_skel_thin(const int32_t* cls, int N, int H, int W, int max_passes, int32_t* out,
                                   int32_t* unconverged, void* ws, size_t ws_bytes, void* stream) {
   US_CHECK_ARG(cls && out && ws, "skel_thin: null pointer");  // unconverged may be NULL
-  US_CHECK_ARG(skel_shape_ok(N, H, W), "skel_thin: bad shape N=%d H=%d W=%d", N, H, W);
+  US_CHECK_ARG(SkelTiles::shape_ok(N, H, W), "skel_thin: bad shape N=%d H=%d W=%d", N, H, W);
   US_CHECK_ARG(max_passes >= 0, "skel_thin: max_passes %d must not be negative", max_passes);
   US_CHECK_ARG(ws_bytes >= unetseg_skel_workspace(N, H, W), "skel_thin: workspace too small");
   US_CHECK_ARG(((uintptr_t)ws & 15) == 0, "skel_thin: the workspace must be 16-byte aligned");
@@ -350,7 +337,7 @@ UNETSEG_API int unetseg_skel_counts(const int32_t* pred, const int32_t* target, 
                                     void* stream) {
   US_CHECK_ARG(pred && target && skel_pred && skel_target && unconv_pred && unconv_target && out,
                "skel_counts: null pointer");
-  US_CHECK_ARG(skel_shape_ok(N, H, W), "skel_counts: bad shape N=%d H=%d W=%d", N, H, W);
+  US_CHECK_ARG(SkelTiles::shape_ok(N, H, W), "skel_counts: bad shape N=%d H=%d W=%d", N, H, W);
   US_CHECK_ARG(c >= 1 && c <= kMaxClass, "skel_counts: class %d outside 1 .. %d", c, kMaxClass);
   US_CHECK_ARG(ignore != c, "skel_counts: ignore is the counted class %d", c);
   const long total = (long)N * H * W;  // <= 2^40: a block's 32-bit counters hold its share (1024 blocks)

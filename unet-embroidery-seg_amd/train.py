@@ -50,7 +50,7 @@ from utils.train_and_eval import (  # noqa: E402
     train_one_epoch_binary,
     train_one_epoch_multitask,
 )
-from utils.utils import seed_everything, worker_init_fn  # noqa: E402
+from utils.utils import check_loss_term_args, seed_everything, worker_init_fn  # noqa: E402
 
 
 def create_model(model_name, num_classes, weights, num_seg_classes=1, num_cls_classes=3):
@@ -331,18 +331,9 @@ def parse_args(argv=None):
     p.add_argument("--synthetic-val", default=16, type=int, help="synthetic val/test images")
     p.add_argument("--out-dir", default="logs")
     args = p.parse_args(argv)
-    if args.boundary_loss_weight < 0:
-        p.error("--boundary-loss-weight must be >= 0")
-    if args.task == "multiclass" and (args.boundary_loss_weight > 0 or args.boundary_loss_pixels):
-        p.error("--boundary-loss-weight / --boundary-loss-pixels apply to --task binary and multitask only")
+    check_loss_term_args(p, args)
     if args.skeleton_max_passes is not None and args.skeleton_max_passes < 0:
         p.error("--skeleton-max-passes must be >= 0")
-    if args.cldice_weight < 0:
-        p.error("--cldice-weight must be >= 0")
-    if not 0 <= args.cldice_iters <= 64:
-        p.error("--cldice-iters must be 0 .. 64")
-    if args.task == "multiclass" and (args.cldice_weight > 0 or args.cldice_iters != 3):
-        p.error("--cldice-weight / --cldice-iters apply to --task binary and multitask only")
     if args.pos_weight == "":
         args.pos_weight = None
     return args

@@ -49,6 +49,43 @@ def _ignore(ignore_index):
     return int(ignore_index)
 
 
+def _out_counts(out, n, device):
+    """the array a ``counts`` adds to: ``out`` checked, or zeros when it is None"""
+    if out is None:
+        return torch.zeros(n, dtype=torch.int64, device=device)
+    if (not torch.is_tensor(out) or out.dtype != torch.int64 or out.device != device or out.dim() != 1
+            or out.numel() != n or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous int64 [{n}] tensor on {device}")
+    return out
+
+
+def _int_target(target, ignore_index):
+    """an evaluation loop's target [B,H,W] or [B,1,H,W] as int32 [B,H,W]; a float target is read as
+    ``losses.binary_confusion`` reads it: class 1 where it equals 1, ``ignore_index`` kept"""
+    tgt = target.detach()
+    if tgt.is_floating_point():
+        lab = (tgt == 1).to(torch.int32)
+        if ignore_index is not None:
+            lab = torch.where(tgt == ignore_index, torch.full_like(lab, int(ignore_index)), lab)
+        tgt = lab
+    if tgt.dim() == 4 and tgt.shape[1] == 1:
+        tgt = tgt[:, 0]
+    return tgt.to(torch.int32)
+
+
+def _class_mean(rows, several, has_target, read, keys):
+    """an accumulator's metrics from its per-class count rows: ``read(row)`` of the one class, or with
+    ``several`` classes the mean per key over the rows that ``has_target``; 0.0 when none is left"""
+    if several:
+        rows = [r for r in rows if has_target(r)]
+    per = [read(r) for r in rows]
+    if not per:
+        return dict.fromkeys(keys, 0.0)
+    if len(per) == 1:
+        return per[0]
+    return {k: sum(m[k] for m in per) / len(per) for k in keys}
+
+
 def chunk():
     """the distance transform works on column segments and row chunks of this many pixels, so its seams
     lie at the multiples"""
@@ -107,12 +144,7 @@ def counts(pred, target, c=1, K=4096, biou_d=None, ignore_index=None, out=None):
     d = default_biou_d(H, W, K) if biou_d is None else int(biou_d)
     if d < 0 or d * d > K:
         raise ValueError(f"biou_d = {d} px needs 0 <= biou_d^2 <= K = {K}")
-    n = 2 * (K + 2) + 2
-    if out is None:
-        out = torch.zeros(n, dtype=torch.int64, device=p.device)
-    elif (not torch.is_tensor(out) or out.dtype != torch.int64 or out.device != p.device or out.dim() != 1
-          or out.numel() != n or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous int64 [{n}] tensor on {p.device}")
+    out = _out_counts(out, 2 * (K + 2) + 2, p.device)
     ign = _ignore(ignore_index)
     eP, eG = edges(p, c, ignore_index), edges(t, c, ignore_index)
     dP, dG = sqdist(eP), sqdist(eG)
@@ -201,15 +233,7 @@ class Accumulator:
     def add(self, pred, target):
         """pred int32 [B,H,W] (``labels_from_logits``); target [B,H,W] or [B,1,H,W] on the same device, integer,
         or float read as ``losses.binary_confusion`` reads it: class 1 where it equals 1, ``ignore_index`` kept"""
-        tgt = target.detach()
-        if tgt.is_floating_point():
-            lab = (tgt == 1).to(torch.int32)
-            if self.ignore_index is not None:
-                lab = torch.where(tgt == self.ignore_index, torch.full_like(lab, int(self.ignore_index)), lab)
-            tgt = lab
-        if tgt.dim() == 4 and tgt.shape[1] == 1:
-            tgt = tgt[:, 0]
-        tgt = tgt.to(torch.int32)
+        tgt = _int_target(target, self.ignore_index)
         if self.out is None:
             self.out = torch.zeros(len(self.classes), 2 * (self.K + 2) + 2, dtype=torch.int64, device=pred.device)
         for c, out in zip(self.classes, self.out):
@@ -220,11 +244,5 @@ class Accumulator:
         pixel in the split, 0.0 without one"""
         n = 2 * (self.K + 2) + 2
         rows = self.out.tolist() if self.out is not None else [[0] * n for _ in self.classes]
-        if len(self.classes) > 1:
-            rows = [c for c in rows if sum(c[self.K + 2:2 * self.K + 4]) > 0]
-        per = [metrics_from_counts(c, self.K, self.tolerance) for c in rows]
-        if not per:
-            return dict.fromkeys(KEYS, 0.0)
-        if len(per) == 1:
-            return per[0]
-        return {k: sum(m[k] for m in per) / len(per) for k in KEYS}
+        return _class_mean(rows, len(self.classes) > 1, lambda c: sum(c[self.K + 2:2 * self.K + 4]) > 0,
+                           lambda c: metrics_from_counts(c, self.K, self.tolerance), KEYS)

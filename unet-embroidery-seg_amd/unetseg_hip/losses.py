@@ -143,11 +143,15 @@ def _inv_norm(H, W, normalize):
     return 1.0 / math.sqrt(H * H + W * W) if normalize else 1.0
 
 
-def _boundary_forward(out, nch, tgt, H, W, c, ignore_index, normalize, weight, gz, accumulate, phi=None):
-    """unetseg_boundary_loss_fwd on prepared tensors -> the unweighted loss (device scalar); gz (may be
-    None) gets, or with `accumulate` is added, weight * dL/dz"""
+# A term's forward takes (out, nch, tgt, ignore_index, weight, gz, accumulate, *params) on prepared tensors and
+# returns the unweighted loss (device scalar); gz (may be None) gets, or with `accumulate` is added,
+# weight * dL/dz.  A prepared term of a region loss is (forward, weight > 0, params).
+
+
+def _boundary_forward(out, nch, tgt, ignore_index, weight, gz, accumulate, c=1, normalize=True, phi=None):
+    """unetseg_boundary_loss_fwd as a term's forward"""
     dev = out.device
-    B = out.shape[0]
+    B, H, W = out.shape[0], out.shape[-2], out.shape[-1]
     loss = torch.empty((), dtype=torch.float32, device=dev)
     ws = workspace(_q("boundary_loss_workspace", B, H, W), dev)
     lib.boundary_loss_fwd(P(out), nch, P(tgt), B, H, W, int(c), -1 if ignore_index is None else int(ignore_index),
@@ -176,30 +180,10 @@ def _one(dev):
     return t
 
 
-def _add_boundary(region, out, nch, tgt, gz, boundary, ignore_index, one):
-    """region + w * L with the boundary term's gradient added onto the region loss's gz (None: no gradient);
-    boundary = (weight > 0, normalize); `one` a device scalar 1"""
-    w, normalize = boundary
-    H, W = out.shape[-2], out.shape[-1]
-    bl = _boundary_forward(out, nch, tgt, H, W, 1, ignore_index, normalize, w, gz, 1)
-    total = torch.empty((), dtype=torch.float32, device=out.device)
-    lib.scale_grad(P(one), 1, P(region), 1.0, P(bl), float(w), P(total), _stream(out.device))
-    return total
-
-
-def _boundary_arg(weight, normalize):
-    """None for the default weight 0 (nothing is launched), else (weight, normalize)"""
-    weight = float(weight)
-    if weight < 0 or not math.isfinite(weight):
-        raise ValueError(f"boundary_weight must be a finite number >= 0, got {weight}")
-    return (weight, bool(normalize)) if weight > 0 else None
-
-
-def _cldice_forward(out, nch, tgt, H, W, ignore_index, iters, smooth, weight, gz, accumulate):
-    """unetseg_cldice_fwd on prepared tensors -> the unweighted loss (device scalar); gz (may be None) gets,
-    or with `accumulate` is added, weight * dL/dz"""
+def _cldice_forward(out, nch, tgt, ignore_index, weight, gz, accumulate, iters=3, smooth=1.0):
+    """unetseg_cldice_fwd as a term's forward"""
     dev = out.device
-    B = out.shape[0]
+    B, H, W = out.shape[0], out.shape[-2], out.shape[-1]
     loss = torch.empty((), dtype=torch.float32, device=dev)
     ws = workspace(_q("cldice_workspace", B, H, W, int(iters)), dev)
     lib.cldice_fwd(P(out), nch, P(tgt), B, H, W, -1 if ignore_index is None else int(ignore_index), int(iters),
@@ -207,15 +191,21 @@ def _cldice_forward(out, nch, tgt, H, W, ignore_index, iters, smooth, weight, gz
     return loss
 
 
-def _add_cldice(region, out, nch, tgt, gz, cldice, ignore_index, one):
-    """region + w * L with the clDice term's gradient added onto the region loss's gz (None: no gradient);
-    cldice = (weight > 0, iters); `one` a device scalar 1"""
-    w, iters = cldice
-    H, W = out.shape[-2], out.shape[-1]
-    cl = _cldice_forward(out, nch, tgt, H, W, ignore_index, iters, 1.0, w, gz, 1)
+def _add_term(region, term, out, nch, tgt, gz, ignore_index, one):
+    """region + w * L with the term's gradient added onto the region loss's gz (None: no gradient); `one` a
+    device scalar 1"""
+    forward, w, params = term
+    loss = forward(out, nch, tgt, ignore_index, w, gz, 1, *params)
     total = torch.empty((), dtype=torch.float32, device=out.device)
-    lib.scale_grad(P(one), 1, P(region), 1.0, P(cl), float(w), P(total), _stream(out.device))
+    lib.scale_grad(P(one), 1, P(region), 1.0, P(loss), float(w), P(total), _stream(out.device))
     return total
+
+
+def _term_weight(name, weight):
+    weight = float(weight)
+    if weight < 0 or not math.isfinite(weight):
+        raise ValueError(f"{name} must be a finite number >= 0, got {weight}")
+    return weight
 
 
 def _check_iters(iters):
@@ -224,41 +214,48 @@ def _check_iters(iters):
     return int(iters)
 
 
-def _cldice_arg(weight, iters):
-    """None for the default weight 0 (nothing is launched), else (weight, iters)"""
-    weight = float(weight)
-    if weight < 0 or not math.isfinite(weight):
-        raise ValueError(f"cldice_weight must be a finite number >= 0, got {weight}")
-    iters = _check_iters(iters)
-    return (weight, iters) if weight > 0 else None
+def _terms(boundary_weight, boundary_normalize, cldice_weight, cldice_iters):
+    """the prepared terms of a region loss in the order they are added: the boundary loss of class 1, then the
+    soft clDice.  A term of the default weight 0 is left out (nothing is launched)."""
+    bw = _term_weight("boundary_weight", boundary_weight)
+    cw = _term_weight("cldice_weight", cldice_weight)
+    iters = _check_iters(cldice_iters)
+    terms = ()
+    if bw > 0:
+        terms += ((_boundary_forward, bw, (1, bool(boundary_normalize))),)
+    if cw > 0:
+        terms += ((_cldice_forward, cw, (iters, 1.0)),)
+    return terms
+
+
+def _dout_from_gz(fctx, g):
+    """the backward of a loss that saved gz = dL/dz [B, Pn]: g * gz on the logit channels, in the input dtype"""
+    (gz,) = fctx.saved_tensors
+    B, nch, Pn, shape, dtype = fctx.meta
+    g = g.detach().float().reshape(1).contiguous()
+    dout = torch.empty(shape, dtype=torch.float32, device=gz.device)
+    scratch = torch.empty_like(gz)
+    lib.dz_to_dout(P(gz), B, Pn, nch, P(g), 1.0, 0, 0.0, P(scratch), P(dout), _stream(gz.device))
+    return dout.to(dtype)
 
 
 class _SegLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(fctx, outputs, targets, kind, pos_weight, ignore_index=None, boundary=None, cldice=None):
+    def forward(fctx, outputs, targets, kind, pos_weight, ignore_index=None, terms=()):
         out, tgt, _ = _prep(outputs, targets, ignore_index)
         B, nch = out.shape[0], out.shape[1]
         Pn = out[0, 0].numel()
         loss, gz = _seg_forward(kind, out, nch, tgt, B, Pn, pos_weight, outputs.requires_grad, ignore_index)
-        if boundary is not None:
-            loss = _add_boundary(loss, out, nch, tgt, gz if outputs.requires_grad else None, boundary, ignore_index,
-                                 _one(out.device))
-        if cldice is not None:
-            loss = _add_cldice(loss, out, nch, tgt, gz if outputs.requires_grad else None, cldice, ignore_index,
-                               _one(out.device))
+        for term in terms:
+            loss = _add_term(loss, term, out, nch, tgt, gz if outputs.requires_grad else None, ignore_index,
+                             _one(out.device))
         fctx.save_for_backward(gz)
         fctx.meta = (B, nch, Pn, outputs.shape, outputs.dtype)
         return loss
 
     @staticmethod
     def backward(fctx, g):
-        (gz,) = fctx.saved_tensors
-        B, nch, Pn, shape, dtype = fctx.meta
-        g = g.detach().float().reshape(1).contiguous()
-        dout = torch.empty(shape, dtype=torch.float32, device=gz.device)
-        scratch = torch.empty_like(gz)
-        lib.dz_to_dout(P(gz), B, Pn, nch, P(g), 1.0, 0, 0.0, P(scratch), P(dout), _stream(gz.device))
-        return dout.to(dtype), None, None, None, None, None, None
+        return _dout_from_gz(fctx, g), None, None, None, None, None
 
 
 def binary_segmentation_loss(outputs, targets, loss_name, pos_weight=None, ignore_index=None, boundary_weight=0.0,
@@ -275,8 +272,7 @@ def binary_segmentation_loss(outputs, targets, loss_name, pos_weight=None, ignor
     if loss_name not in ("bce", "lovasz_hinge"):
         raise ValueError(f"Unsupported loss_name: {loss_name}")
     return _SegLossFn.apply(outputs, targets, loss_name, pos_weight, ignore_index,
-                            _boundary_arg(boundary_weight, boundary_normalize),
-                            _cldice_arg(cldice_weight, cldice_iters))
+                            _terms(boundary_weight, boundary_normalize, cldice_weight, cldice_iters))
 
 
 def _logits_4d(outputs):
@@ -287,28 +283,24 @@ def _logits_4d(outputs):
     return outputs
 
 
-class _BoundaryLossFn(torch.autograd.Function):
+class _TermLossFn(torch.autograd.Function):
+    """one term on its own: `forward` with `params`, weight 1, writing gz"""
+
     @staticmethod
-    def forward(fctx, outputs, targets, c, ignore_index, normalize):
+    def forward(fctx, outputs, targets, name, forward, ignore_index, params):
         out, tgt, _ = _prep(outputs, targets, ignore_index)
         B, nch, H, W = out.shape
         if tuple(tgt.shape) != (B, H, W):
-            raise ValueError(f"boundary_loss: targets {tuple(targets.shape)} do not match logits {tuple(outputs.shape)}")
+            raise ValueError(f"{name}: targets {tuple(targets.shape)} do not match logits {tuple(outputs.shape)}")
         gz = torch.empty((B, H * W), dtype=torch.float32, device=out.device) if outputs.requires_grad else None
-        loss = _boundary_forward(out, nch, tgt, H, W, c, ignore_index, normalize, 1.0, gz, 0)
+        loss = forward(out, nch, tgt, ignore_index, 1.0, gz, 0, *params)
         fctx.save_for_backward(gz)
         fctx.meta = (B, nch, H * W, outputs.shape, outputs.dtype)
         return loss
 
     @staticmethod
     def backward(fctx, g):
-        (gz,) = fctx.saved_tensors
-        B, nch, Pn, shape, dtype = fctx.meta
-        g = g.detach().float().reshape(1).contiguous()
-        dout = torch.empty(shape, dtype=torch.float32, device=gz.device)
-        scratch = torch.empty_like(gz)
-        lib.dz_to_dout(P(gz), B, Pn, nch, P(g), 1.0, 0, 0.0, P(scratch), P(dout), _stream(gz.device))
-        return dout.to(dtype), None, None, None, None
+        return _dout_from_gz(fctx, g), None, None, None, None, None
 
 
 def boundary_loss(outputs, targets, c=1, ignore_index=None, normalize=True):
@@ -317,7 +309,8 @@ def boundary_loss(outputs, targets, c=1, ignore_index=None, normalize=True):
     [B,2,H,W] (z = o1 - o0), [B,1,H,W] or [B,H,W]; targets [B,H,W].  normalize divides by the image diagonal
     sqrt(H^2 + W^2), so the value lies in [-1, 1] at every input size; False gives the paper's pixel units.
     Meant to be added to a region loss with a small weight (boundary_weight= of the region losses)."""
-    return _BoundaryLossFn.apply(_logits_4d(outputs), targets, int(c), ignore_index, normalize)
+    return _TermLossFn.apply(_logits_4d(outputs), targets, "boundary_loss", _boundary_forward, ignore_index,
+                             (int(c), normalize))
 
 
 def signed_distance(targets, c=1, ignore_index=None):
@@ -330,32 +323,8 @@ def signed_distance(targets, c=1, ignore_index=None):
     B, H, W = tgt.shape
     out = torch.zeros((B, 1, H, W), dtype=torch.float32, device=tgt.device)
     phi = torch.empty((B, H, W), dtype=torch.float32, device=tgt.device)
-    _boundary_forward(out, 1, tgt, H, W, int(c), ignore_index, False, 0.0, None, 0, phi)
+    _boundary_forward(out, 1, tgt, ignore_index, 0.0, None, 0, int(c), False, phi)
     return phi
-
-
-class _ClDiceLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(fctx, outputs, targets, iters, smooth, ignore_index):
-        out, tgt, _ = _prep(outputs, targets, ignore_index)
-        B, nch, H, W = out.shape
-        if tuple(tgt.shape) != (B, H, W):
-            raise ValueError(f"cldice_loss: targets {tuple(targets.shape)} do not match logits {tuple(outputs.shape)}")
-        gz = torch.empty((B, H * W), dtype=torch.float32, device=out.device) if outputs.requires_grad else None
-        loss = _cldice_forward(out, nch, tgt, H, W, ignore_index, iters, smooth, 1.0, gz, 0)
-        fctx.save_for_backward(gz)
-        fctx.meta = (B, nch, H * W, outputs.shape, outputs.dtype)
-        return loss
-
-    @staticmethod
-    def backward(fctx, g):
-        (gz,) = fctx.saved_tensors
-        B, nch, Pn, shape, dtype = fctx.meta
-        g = g.detach().float().reshape(1).contiguous()
-        dout = torch.empty(shape, dtype=torch.float32, device=gz.device)
-        scratch = torch.empty_like(gz)
-        lib.dz_to_dout(P(gz), B, Pn, nch, P(g), 1.0, 0, 0.0, P(scratch), P(dout), _stream(gz.device))
-        return dout.to(dtype), None, None, None, None
 
 
 def cldice_loss(outputs, targets, iters=3, smooth=1.0, ignore_index=None):
@@ -368,7 +337,8 @@ def cldice_loss(outputs, targets, iters=3, smooth=1.0, ignore_index=None):
     smooth = float(smooth)
     if not (smooth > 0 and math.isfinite(smooth)):
         raise ValueError(f"cldice_loss: smooth must be a finite number > 0, got {smooth}")
-    return _ClDiceLossFn.apply(_logits_4d(outputs), targets, _check_iters(iters), smooth, ignore_index)
+    return _TermLossFn.apply(_logits_4d(outputs), targets, "cldice_loss", _cldice_forward, ignore_index,
+                             (_check_iters(iters), smooth))
 
 
 class _SoftSkelFn(torch.autograd.Function):
@@ -413,20 +383,16 @@ def seg_loss_1ch(logits, targets, kind):
 
 class _MultiTaskFn(torch.autograd.Function):
     @staticmethod
-    def forward(fctx, seg, cls, seg_t, cls_t, w, kind, boundary=None, cldice=None):
+    def forward(fctx, seg, cls, seg_t, cls_t, w, kind, terms=()):
         out, tgt, soft = _prep(seg, seg_t)
         B = out.shape[0]
         Pn = out[0].numel()
         dev = out.device
         seg_loss, gz = _seg_forward(kind, out, 1, tgt, B, Pn, None, True)
-        one = None
-        if boundary is not None:
-            one = torch.ones(1, dtype=torch.float32, device=dev)
-            seg_loss = _add_boundary(seg_loss, out, 1, tgt, gz, boundary, None, one)
-        if cldice is not None:
-            if one is None:
-                one = torch.ones(1, dtype=torch.float32, device=dev)
-            seg_loss = _add_cldice(seg_loss, out, 1, tgt, gz, cldice, None, one)
+        # the constant 1 of every scale_grad below, made once a call, where it is first read
+        one = torch.ones(1, dtype=torch.float32, device=dev) if terms else None
+        for term in terms:
+            seg_loss = _add_term(seg_loss, term, out, 1, tgt, gz, None, one)
         if kind == "bce":
             _poison(soft, seg_loss, gz)
         c = cls.detach().float().contiguous()
@@ -462,7 +428,7 @@ class _MultiTaskFn(torch.autograd.Function):
         lib.dz_to_dout(P(gz), B, Pn, 1, P(tmp), 1.0, 0, 0.0, P(scratch), P(dseg), st)
         dcls = torch.empty_like(dlog)
         lib.scale_grad(P(dlog), dlog.numel(), P(gt), w, P(gc), 1.0, P(dcls), st)
-        return dseg, dcls, None, None, None, None, None, None
+        return dseg, dcls, None, None, None, None, None
 
 
 def multitask_loss(seg_logits, cls_logits, seg_targets, cls_targets, cls_loss_weight=1.0, kind="bce",
@@ -471,8 +437,7 @@ def multitask_loss(seg_logits, cls_logits, seg_targets, cls_targets, cls_loss_we
     logits to seg_loss (and so to total), its gradient onto the seg term's (see binary_segmentation_loss);
     cldice_weight > 0 does the same with cldice_loss(seg logits, seg targets, iters=cldice_iters)."""
     return _MultiTaskFn.apply(seg_logits, cls_logits, seg_targets, cls_targets, cls_loss_weight, kind,
-                              _boundary_arg(boundary_weight, boundary_normalize),
-                              _cldice_arg(cldice_weight, cldice_iters))
+                              _terms(boundary_weight, boundary_normalize, cldice_weight, cldice_iters))
 
 
 def binary_confusion(outputs, targets, conf=None, ignore_index=None):

@@ -16,7 +16,7 @@ import ctypes
 
 import torch
 
-from .boundary import _ignore, _map, _stream
+from .boundary import _class_mean, _ignore, _int_target, _map, _out_counts, _stream
 from .lib import lib
 
 KEYS = ("clDice", "Skeleton Precision", "Skeleton Recall")
@@ -77,15 +77,6 @@ def _check_class(c, ignore_index):
     return c
 
 
-def _out6(out, device):
-    if out is None:
-        return torch.zeros(6, dtype=torch.int64, device=device)
-    if (not torch.is_tensor(out) or out.dtype != torch.int64 or out.device != device or out.dim() != 1
-            or out.numel() != 6 or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous int64 [6] tensor on {device}")
-    return out
-
-
 def _pair(pred, target, ignore_index):
     """pred and target as [N,H,W], with the pixels whose target is ``ignore_index`` set to 0 in both"""
     p, t = _map(pred, "pred"), _map(target, "target")
@@ -127,7 +118,7 @@ def counts(pred, target, c=1, ignore_index=None, max_passes=None, out=None):
     c = _check_class(c, ignore_index)
     ign = _ignore(ignore_index)
     p, t, pm, tm = _pair(pred, target, ignore_index)
-    out = _out6(out, p.device)
+    out = _out_counts(out, 6, p.device)
     return _counts(pm, t, _thin_pair(pm, tm, max_passes), c, ign, out)
 
 
@@ -172,15 +163,7 @@ class Accumulator:
 
     def add(self, pred, target):
         """pred int32 [B,H,W] (``boundary.labels_from_logits``); target as ``boundary.Accumulator.add`` takes it"""
-        tgt = target.detach()
-        if tgt.is_floating_point():
-            lab = (tgt == 1).to(torch.int32)
-            if self.ignore_index is not None:
-                lab = torch.where(tgt == self.ignore_index, torch.full_like(lab, int(self.ignore_index)), lab)
-            tgt = lab
-        if tgt.dim() == 4 and tgt.shape[1] == 1:
-            tgt = tgt[:, 0]
-        tgt = tgt.to(torch.int32)
+        tgt = _int_target(target, self.ignore_index)
         if self.out is None:
             self.out = torch.zeros(len(self.classes), 6, dtype=torch.int64, device=pred.device)
         p, t, pm, tm = _pair(pred, tgt, self.ignore_index)
@@ -195,11 +178,4 @@ class Accumulator:
         for r in rows:  # an unconverged image spoils every class's counts
             if r[4] > 0:
                 metrics_from_counts(r)
-        if len(self.classes) > 1:
-            rows = [r for r in rows if r[3] > 0]
-        per = [metrics_from_counts(r) for r in rows]
-        if not per:
-            return dict.fromkeys(KEYS, 0.0)
-        if len(per) == 1:
-            return per[0]
-        return {k: sum(m[k] for m in per) / len(per) for k in KEYS}
+        return _class_mean(rows, len(self.classes) > 1, lambda r: r[3] > 0, metrics_from_counts, KEYS)

@@ -163,19 +163,19 @@ def train_one_epoch_binary(model, optimizer, train_loader, device, loss_name: st
     return float(epoch_loss.item()) / max(seen_batches, 1)
 
 
-def _boundary_acc(boundary, classes=(1,), ignore_index=None):
-    """the boundary-count accumulator of an evaluation loop, or None without the `boundary` options"""
-    return None if boundary is None else BoundaryAccumulator(boundary, classes, ignore_index)
-
-
-def _skeleton_acc(skeleton, classes=(1,), ignore_index=None):
-    """the skeleton-count accumulator (clDice metric) of an evaluation loop, or None without the `skeleton` options"""
-    return None if skeleton is None else SkeletonAccumulator(skeleton, classes, ignore_index)
+def _metric_accs(boundary, skeleton, classes=(1,), ignore_index=None):
+    """the count accumulators of an evaluation loop, in the order their keys enter the metrics: the boundary
+    counts with the `boundary` options, the skeleton counts (clDice metric) with the `skeleton` options"""
+    accs = []
+    if boundary is not None:
+        accs.append(BoundaryAccumulator(boundary, classes, ignore_index))
+    if skeleton is not None:
+        accs.append(SkeletonAccumulator(skeleton, classes, ignore_index))
+    return accs
 
 
 def _add_counts(accs, logits, targets):
     """one class map of the logits for the accumulators that are on"""
-    accs = [a for a in accs if a is not None]
     if accs:
         pred = labels_from_logits(logits)
         for a in accs:
@@ -192,8 +192,7 @@ def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignor
     skeleton: None, or {"max_passes": int or None} to add clDice, Skeleton Precision and Skeleton Recall of class 1
     on hard skeletons (unetseg_hip/skeleton.py), counted on the device and pooled over the split."""
     model_eval = model.eval().to(device)
-    bacc = _boundary_acc(boundary, (1,), ignore_index)
-    sacc = _skeleton_acc(skeleton, (1,), ignore_index)
+    accs = _metric_accs(boundary, skeleton, (1,), ignore_index)
     total_loss = torch.zeros((), dtype=torch.float64, device=device)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     seen_batches = 0
@@ -205,17 +204,15 @@ def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignor
                                             boundary_normalize, cldice_weight, cldice_iters)
             total_loss += loss
             losses.binary_confusion(outputs, pngs, conf, ignore_index)
-            _add_counts((bacc, sacc), outputs, pngs)
+            _add_counts(accs, outputs, pngs)
             seen_batches += 1
             if max_batches is not None and seen_batches >= max_batches:
                 break
     tp, fp, fn, tn = (float(v) for v in conf.tolist())
     metrics = binary_segmentation_metrics(tp, fp, fn, tn)
     metrics["Loss"] = float(total_loss.item() / max(seen_batches, 1))
-    if bacc is not None:
-        metrics.update(bacc.metrics())
-    if sacc is not None:
-        metrics.update(sacc.metrics())
+    for a in accs:
+        metrics.update(a.metrics())
     return metrics
 
 
@@ -261,8 +258,7 @@ def evaluate_multitask(model, loader, device, criterion, max_batches=None, bound
     with P = sigmoid(seg) > 0.5 (fused confusion kernel, u64 counts on the device); cls accuracy %.
     boundary, skeleton: as in evaluate_binary, on the segmentation head."""
     model.eval()
-    bacc = _boundary_acc(boundary)
-    sacc = _skeleton_acc(skeleton)
+    accs = _metric_accs(boundary, skeleton)
     sums = torch.zeros(3, dtype=torch.float64, device=device)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     correct = torch.zeros((), dtype=torch.int64, device=device)
@@ -277,7 +273,7 @@ def evaluate_multitask(model, loader, device, criterion, max_batches=None, bound
             loss, seg_loss, cls_loss = criterion(seg_logits, cls_logits, seg_targets, cls_targets)
             sums += torch.stack([loss, seg_loss, cls_loss]).double()
             losses.binary_confusion(seg_logits, seg_targets, conf)
-            _add_counts((bacc, sacc), seg_logits, seg_targets)
+            _add_counts(accs, seg_logits, seg_targets)
             correct += cls_logits.argmax(1).eq(cls_targets).sum()
             total += cls_targets.size(0)
     tp, fp, fn, _tn = (float(v) for v in conf.tolist())
@@ -287,10 +283,8 @@ def evaluate_multitask(model, loader, device, criterion, max_batches=None, bound
     metrics = {"Loss": l, "Seg Loss": sl, "Cls Loss": cl, "IoU": tp / (tp + fp + fn + 1e-6),
                "Dice": 2 * tp / ((tp + fp) + (tp + fn) + 1e-6),
                "Cls Acc": 100.0 * float(correct.item()) / max(total, 1)}
-    if bacc is not None:
-        metrics.update(bacc.metrics())
-    if sacc is not None:
-        metrics.update(sacc.metrics())
+    for a in accs:
+        metrics.update(a.metrics())
     return metrics
 
 
@@ -380,8 +374,7 @@ def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lova
     skeleton: None, or {"max_passes": int or None} to add the clDice metrics in the same way: the mean over the
     classes whose target skeleton is non-empty in the split."""
     import numpy as np
-    bacc = _boundary_acc(boundary, tuple(range(1, num_classes)), num_classes)
-    sacc = _skeleton_acc(skeleton, tuple(range(1, num_classes)), num_classes)
+    accs = _metric_accs(boundary, skeleton, tuple(range(1, num_classes)), num_classes)
     weights = torch.tensor(np.ones([num_classes], np.float32)).to(device)
     model_eval = model.eval().to(device)
     hists, loss_sum = [], torch.zeros((), dtype=torch.float64, device=device)
@@ -392,7 +385,7 @@ def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lova
             loss_sum += _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss,
                                  lovasz_softmax).double()
             hists.append(losses.mc_confusion(outputs, pngs))
-            _add_counts((bacc, sacc), outputs, pngs)
+            _add_counts(accs, outputs, pngs)
     n = max(len(val_loader), 1)
     keys = ("Pixel Accuracy", "Mean Accuracy", "Mean IoU", "Frequency Weighted IoU")
     tot = dict.fromkeys(keys, 0.0)
@@ -402,8 +395,6 @@ def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lova
             tot[k] += m[k]
     metrics = {k: tot[k] / n for k in keys}
     metrics["Loss"] = float(loss_sum.item()) / n
-    if bacc is not None:
-        metrics.update(bacc.metrics())
-    if sacc is not None:
-        metrics.update(sacc.metrics())
+    for a in accs:
+        metrics.update(a.metrics())
     return metrics

@@ -20,6 +20,20 @@ def seed_everything(seed=11):
     torch.backends.cudnn.benchmark = False
 
 
+def check_loss_term_args(parser, args):
+    """train.py's and val.py's --boundary-loss-* and --cldice-* options: parser.error on a bad value or task"""
+    if args.boundary_loss_weight < 0:
+        parser.error("--boundary-loss-weight must be >= 0")
+    if args.task == "multiclass" and (args.boundary_loss_weight > 0 or args.boundary_loss_pixels):
+        parser.error("--boundary-loss-weight / --boundary-loss-pixels apply to --task binary and multitask only")
+    if args.cldice_weight < 0:
+        parser.error("--cldice-weight must be >= 0")
+    if not 0 <= args.cldice_iters <= 64:
+        parser.error("--cldice-iters must be 0 .. 64")
+    if args.task == "multiclass" and (args.cldice_weight > 0 or args.cldice_iters != 3):
+        parser.error("--cldice-weight / --cldice-iters apply to --task binary and multitask only")
+
+
 def worker_init_fn(worker_id, seed=0):
     worker_seed = worker_id + seed
     random.seed(worker_seed)

@@ -38,6 +38,7 @@ from unetseg_hip.tta import MODES as TTA_MODES, TTA  # noqa: E402
 from utils.hf_dataloader import DeviceLoader, HFUnetDataset, make_collate  # noqa: E402
 from utils.synthetic import SyntheticSegDataset, collate  # noqa: E402
 from utils.train_and_eval import LogColor, evaluate, evaluate_binary  # noqa: E402
+from utils.utils import check_loss_term_args  # noqa: E402
 
 CLASS_NAMES = ["动物类", "植物类", "复合类"]  # val.py:84
 
@@ -206,16 +207,7 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.skeleton_max_passes is not None and args.skeleton_max_passes < 0:
         p.error("--skeleton-max-passes must be >= 0")
-    if args.cldice_weight < 0:
-        p.error("--cldice-weight must be >= 0")
-    if not 0 <= args.cldice_iters <= 64:
-        p.error("--cldice-iters must be 0 .. 64")
-    if args.task == "multiclass" and (args.cldice_weight > 0 or args.cldice_iters != 3):
-        p.error("--cldice-weight / --cldice-iters apply to --task binary and multitask only")
-    if args.boundary_loss_weight < 0:
-        p.error("--boundary-loss-weight must be >= 0")
-    if args.task == "multiclass" and (args.boundary_loss_weight > 0 or args.boundary_loss_pixels):
-        p.error("--boundary-loss-weight / --boundary-loss-pixels apply to --task binary and multitask only")
+    check_loss_term_args(p, args)
     return args
 
 
