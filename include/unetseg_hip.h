@@ -698,7 +698,8 @@ int unetseg_linear_bwd(const float* dy, const float* pre, const float* mask, flo
                        void* stream);
 
 /* ---- optimizer: torch.optim.Adam with coupled weight decay (train.py:62-78) over one flat fp32
- *      arena; grad_scale (may be NULL) multiplies g first ------------------------------------------ */
+ *      arena; grad_scale (device pointer, may be NULL) is the loss scale the gradients carry: g is
+ *      divided by grad_scale[0] first (GradScaler's unscale), as g * (1 / grad_scale[0]) ------------ */
 int unetseg_adam(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
                  float wd, int step, const float* grad_scale, void* stream);
 /* capturable Adam (hipGraph replay): hyper[0] = lr and *step (steps taken; advanced by one after the

@@ -203,6 +203,24 @@ static void argument_checks() {
           "softmax_resize crop outside");
   refused(unetseg_adam(nullptr, DF, DF, DF, 10, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 1, nullptr, nullptr), "adam null p");
   refused(unetseg_adam(DF, DF, DF, DF, 10, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 0, nullptr, nullptr), "adam step 0");
+  {
+    int* const DI = reinterpret_cast<int*>(D);
+    refused(unetseg_adam_dev(nullptr, DF, DF, DF, 10, DF, DI, 0.9f, 0.999f, 1e-8f, 0.f, nullptr, nullptr),
+            "adam_dev null p");
+    refused(unetseg_adam_dev(DF, nullptr, DF, DF, 10, DF, DI, 0.9f, 0.999f, 1e-8f, 0.f, nullptr, nullptr),
+            "adam_dev null g");
+    refused(unetseg_adam_dev(DF, DF, nullptr, DF, 10, DF, DI, 0.9f, 0.999f, 1e-8f, 0.f, nullptr, nullptr),
+            "adam_dev null m");
+    refused(unetseg_adam_dev(DF, DF, DF, nullptr, 10, DF, DI, 0.9f, 0.999f, 1e-8f, 0.f, nullptr, nullptr),
+            "adam_dev null v");
+    refused(unetseg_adam_dev(DF, DF, DF, DF, -1, DF, DI, 0.9f, 0.999f, 1e-8f, 0.f, nullptr, nullptr),
+            "adam_dev n<0");
+    refused(unetseg_adam_dev(DF, DF, DF, DF, 10, nullptr, DI, 0.9f, 0.999f, 1e-8f, 0.f, nullptr, nullptr),
+            "adam_dev null hyper");
+    refused(unetseg_adam_dev(DF, DF, DF, DF, 10, DF, nullptr, 0.9f, 0.999f, 1e-8f, 0.f, nullptr, nullptr),
+            "adam_dev null step");
+    refused(unetseg_adam(DF, DF, DF, DF, -1, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 1, nullptr, nullptr), "adam n<0");
+  }
   refused(unetseg_linear_fwd(nullptr, DF, DF, 2, 8, 8, 0, 0.f, 0, nullptr, nullptr, nullptr, DF, nullptr),
           "linear_fwd null x");
   refused(unetseg_ce_fwd(DF, reinterpret_cast<const int64_t*>(D), 0, 3, DF, DF, nullptr), "ce B=0");

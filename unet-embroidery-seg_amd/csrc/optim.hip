@@ -76,6 +76,7 @@ UNETSEG_API int unetseg_adam(float* p, const float* g, float* m, float* v, long 
 UNETSEG_API int unetseg_adam_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step,
                                  float beta1, float beta2, float eps, float wd, const float* grad_scale,
                                  void* stream) {
+  US_CHECK_ARG(p && g && m && v && n >= 0, "adam_dev: null pointer or negative size");
   US_CHECK_ARG(hyper && step, "adam_dev: hyper and step must be device pointers");
   hipLaunchKernelGGL(adam_dev_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, step,
                      beta1, beta2, eps, wd, grad_scale);

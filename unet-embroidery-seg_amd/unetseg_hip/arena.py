@@ -58,9 +58,13 @@ class FusedAdam(torch.optim.Optimizer):
             b.finish_actions.append(self._bucket_finish)
 
     def _state(self, flat):
-        if self._m is None or self._m.device != flat.device:
+        if self._m is None:
             self._m = torch.zeros_like(flat)
             self._v = torch.zeros_like(flat)
+        elif self._m.device != flat.device:
+            # loaded moments (a checkpoint read with map_location) or a model moved since: they follow the arena
+            self._m = self._m.to(flat.device)
+            self._v = self._v.to(flat.device)
 
     def _bucket_update(self, i, s, e, stream):
         """Adam over the arena slice [s, e) + re-pack of its convs, on `stream` (GradBuckets action)"""
@@ -148,9 +152,24 @@ class FusedAdam(torch.optim.Optimizer):
         return sd
 
     def load_state_dict(self, sd):
-        fs = sd.pop("flat_state", None)
-        super().load_state_dict(sd)
+        """the caller's dict is left as it was; the moments are copied (the kernels update them in place) onto
+        the arena's device, and must match the arena's size"""
+        fs = sd.get("flat_state")
+        m = v = None
+        if fs is not None:  # refused before anything is loaded
+            flat = self.model._flat
+            m, v = fs["exp_avg"], fs["exp_avg_sq"]
+            if (m is None) != (v is None):
+                raise ValueError("FusedAdam.load_state_dict: exp_avg and exp_avg_sq must both be present or both None")
+            for name, t in (("exp_avg", m), ("exp_avg_sq", v)):
+                if t is not None and tuple(t.shape) != tuple(flat.shape):
+                    raise ValueError(f"FusedAdam.load_state_dict: {name} has shape {tuple(t.shape)}, the "
+                                     f"parameter arena {tuple(flat.shape)}")
+        super().load_state_dict({k: val for k, val in sd.items() if k != "flat_state"})
         if fs is not None:
-            self._step = fs["step"]
-            self._m, self._v = fs["exp_avg"], fs["exp_avg_sq"]
+            if m is not None:
+                m = m.detach().to(device=flat.device, dtype=torch.float32, copy=True).contiguous()
+                v = v.detach().to(device=flat.device, dtype=torch.float32, copy=True).contiguous()
+            self._step = int(fs["step"])
+            self._m, self._v = m, v
             self._hyper = self._step_dev = None  # rebuilt from the host values at the next step
