@@ -643,6 +643,32 @@ int unetseg_skel_counts(const int32_t* pred, const int32_t* target, const int32_
                         const int32_t* skel_target, const int32_t* unconv_pred, const int32_t* unconv_target, int N,
                         int H, int W, int c, int ignore, int64_t* out /* [6], accumulates */, void* stream);
 
+/* ---- score histogram of the binary head: operating-point and calibration metrics (no reference
+ * ---- counterpart) ---------------------------------------------------------------------------------
+ * unetseg_curve_hist: hist u64 [2][K] += per valid pixel: row = (tgt == 1), column = bin(z).
+ *   Layout.  out is planar fp32 [B][nch][P], nch in {1, 2}; tgt int64 [B][P].
+ *   Score.   z = o0 for nch == 1; for nch == 2, z = o1 - o0, one IEEE fp32 subtraction (as the loss kernels
+ *            form it).
+ *   Edges.   edges is device fp32 [K - 1], ascending, 2 <= K <= unetseg_curve_max_bins() = 4096.
+ *   Bin.     bin(z) = the number of edges theta with z > theta, in 0 .. K - 1.  A value equal to an edge goes
+ *            to the lower bin; NaN compares false everywhere and lands in bin 0; -inf lands in bin 0 and +inf
+ *            in bin K - 1.
+ *   No arithmetic on z beyond that subtraction and comparisons (no expf): a CPU reference that holds the
+ *            same edge array reproduces every count exactly.
+ *   Unsorted edges: the bins are unspecified, but the bin index is computed so that it stays in 0 .. K - 1
+ *            for any edge array: no write leaves hist.
+ *   Ignored. Pixels with tgt == ignore_index are skipped; -1 means none.
+ *   Positives.  A positive is tgt == 1 (the rule of unetseg_confusion); every other valid target is a negative.
+ * One launch on the caller's stream, no host wait; integer counts and integer atomics only, so hist is bitwise
+ * reproducible.  Thresholding at edge k - 1 (prediction = bin >= k, which is z > edges[k - 1]) gives tp / fp /
+ * fn / tn as suffix sums of the two rows.
+ * Checked before any launch: null pointers, nch in {1, 2}, 2 <= K <= 4096, B >= 0, P >= 0, B * P <= 2^40.  An
+ * empty input (B * P == 0) launches nothing and returns 0. */
+int unetseg_curve_max_bins(void); /* host only: the largest K */
+int unetseg_curve_hist(const float* out, int nch, const int64_t* tgt, int B, long P, long ignore_index /* -1: none */,
+                       const float* edges /* [K - 1] */, int K, unsigned long long* hist /* [2][K], accumulates */,
+                       void* stream);
+
 /* ---- device augmentation of the loader (utils/hf_dataloader.py:67-105, 111-180, 183-213) -------
  * Replaces HFUnetDataset.get_random_data + preprocess + hf_unet_dataset_collate for one batch:
  * PIL BICUBIC image / NEAREST mask resize (bit-exact), flip, paste on the grey / zero canvas,

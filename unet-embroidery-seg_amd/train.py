@@ -38,6 +38,7 @@ from model.model_factory import SUPPORTED_MODELS, build_model, load_weights_flex
 from model.unet_multitask import MultiTaskLoss  # noqa: E402
 from model.unet_training import get_lr_scheduler, lovasz_hinge_loss, set_optimizer_lr, weights_init  # noqa: E402
 from unetseg_hip.arena import FusedAdam  # noqa: E402
+from unetseg_hip.curve import Accumulator as CurveAccumulator, write_threshold  # noqa: E402
 from unetseg_hip.ddp import GradBuckets, init_from_env, local_device  # noqa: E402
 from utils.hf_dataloader import DeviceLoader, HFUnetDataset, make_collate  # noqa: E402
 from utils.vis_export import export_binary_visuals  # noqa: E402
@@ -184,6 +185,8 @@ def train(args):
     best_path, last_path = os.path.join(weights_folder, "best.pth"), os.path.join(weights_folder, "last.pth")
     # the clDice metric of the validation and test passes (model selection stays on IoU / Mean IoU)
     skel = {"max_passes": args.skeleton_max_passes} if args.skeleton_metrics else None
+    # the operating-point and calibration keys of the binary head (unetseg_hip/curve.py), the same way
+    crv = {"bins": args.curve_bins} if args.curve_metrics else None
     train_losses, val_losses, history = [], [], []
     t0 = time.time()
     for epoch in range(args.epochs):
@@ -212,12 +215,12 @@ def train(args):
         if rank != 0:
             continue
         if args.task == "multitask":
-            metrics = evaluate_multitask(model, val_loader, device, criterion, mvb, skeleton=skel)
+            metrics = evaluate_multitask(model, val_loader, device, criterion, mvb, skeleton=skel, curve=crv)
             print(f"Val - IoU: {metrics['IoU']:.4f}, Dice: {metrics['Dice']:.4f}, Cls Acc: {metrics['Cls Acc']:.2f}%")
             score = float(metrics["IoU"])
         elif args.task == "binary":
             metrics = evaluate_binary(model, val_loader, device, loss_name=args.loss, pos_weight=pos_weight,
-                                      ignore_index=None, max_batches=mvb, skeleton=skel, **bnd)
+                                      ignore_index=None, max_batches=mvb, skeleton=skel, curve=crv, **bnd)
             score = float(metrics["IoU"])
         else:
             metrics = evaluate(model, val_loader, device, args.use_dice, args.loss == "focal", num_classes,
@@ -229,6 +232,8 @@ def train(args):
             best_score, best_epoch, best_metrics = score, epoch + 1, metrics
             torch.save(model.state_dict(), best_path)
             print(f"New best model saved with score: {best_score:.4f}")
+            if crv is not None:  # the operating point of the kept checkpoint, from the validation split only
+                write_threshold(os.path.join(exp_folder, "threshold.json"), metrics, args.curve_bins)
         torch.save(model.state_dict(), last_path)
 
     if rank == 0:
@@ -247,12 +252,14 @@ def train(args):
             if test_loader is None:
                 pass
             elif args.task == "multitask":
-                test_metrics = evaluate_multitask(model, test_loader, device, criterion, mtest, skeleton=skel)
+                test_metrics = evaluate_multitask(model, test_loader, device, criterion, mtest, skeleton=skel,
+                                                  curve=crv)
             elif args.task == "multiclass":
                 test_metrics = evaluate(model, test_loader, device, True, False, num_classes, skeleton=skel)
             else:
                 test_metrics = evaluate_binary(model, test_loader, device, loss_name=args.loss, pos_weight=pos_weight,
-                                               ignore_index=None, max_batches=mtest, skeleton=skel, **bnd)
+                                               ignore_index=None, max_batches=mtest, skeleton=skel, curve=crv,
+                                               **bnd)
             with open(os.path.join(exp_folder, "test_metrics.json"), "w", encoding="utf-8") as f:
                 json.dump(test_metrics, f, ensure_ascii=False, indent=2)
             # fixed-sample visual export of the test split (train.py:476-486; HF datasets only)
@@ -306,6 +313,12 @@ def parse_args(argv=None):
                         "skeletons (into the metric history); model selection stays on IoU / Mean IoU")
     p.add_argument("--skeleton-max-passes", default=None, type=int,
                    help="cap of the thinning passes; default min(H, W) // 2 + 8")
+    p.add_argument("--curve-metrics", action="store_true",
+                   help="validation and test also report the best-IoU threshold with its IoU and F1, IoU at 0.5, AP, "
+                        "AUROC and ECE of the binary head (into the metric history; --task binary and multitask); "
+                        "threshold.json holds the best epoch's validation threshold; model selection stays on IoU")
+    p.add_argument("--curve-bins", default=1000, type=int,
+                   help="bins K of the score histogram (even, a multiple of 10, at most 4096)")
     p.add_argument("--pos-weight", default="auto")
     p.add_argument("--pos-weight-samples", default=80, type=int)
     p.add_argument("--use-dice", action=argparse.BooleanOptionalAction, default=True)
@@ -334,6 +347,13 @@ def parse_args(argv=None):
     check_loss_term_args(p, args)
     if args.skeleton_max_passes is not None and args.skeleton_max_passes < 0:
         p.error("--skeleton-max-passes must be >= 0")
+    if args.curve_metrics:
+        if args.task == "multiclass":
+            p.error("--curve-metrics needs --task binary or multitask (one-vs-rest softmax scores are out of scope)")
+        try:
+            CurveAccumulator({"bins": args.curve_bins})
+        except ValueError as e:
+            p.error(f"--curve-bins: {e}")
     if args.pos_weight == "":
         args.pos_weight = None
     return args

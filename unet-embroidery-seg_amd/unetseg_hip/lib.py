@@ -153,6 +153,8 @@ SIGNATURES = {
     "unetseg_skel_workspace": (SZ, [I, I, I]),
     "unetseg_skel_thin": (I, [P, I, I, I, I, P, P, P, SZ, P]),
     "unetseg_skel_counts": (I, [P, P, P, P, P, P, I, I, I, I, I, P, P]),
+    "unetseg_curve_max_bins": (I, []),
+    "unetseg_curve_hist": (I, [P, I, P, I, L, L, P, I, P, P]),
 }
 
 #: functions returning a value rather than a status (no RuntimeError on non-zero)
@@ -160,7 +162,7 @@ VALUE_FUNCS = {"conv2d_fwd_mask", "reduce_tiles", "pw_small_tiles", "conv_tile_m
                "conv2d_dgrad_post", "conv2d_dgrad_post_res", "stem_fwd_tile_m", "attn_bwd1_tiles", "pw_small_tile", "conv2d_fwd_config",
                "conv2d_dgrad_config", "conv2d_wgrad_config", "stem_config", "pw_head_tiles", "channel_stats_tiles",
                "augment_tables_len", "pack_tiles",
-               "conv2d_fwd_bnrelu_in_config", "conv2d_fwd_head_ok", "upsample2x_bwd_tiles"}
+               "conv2d_fwd_bnrelu_in_config", "conv2d_fwd_head_ok", "upsample2x_bwd_tiles", "curve_max_bins"}
 
 _lib = None
 

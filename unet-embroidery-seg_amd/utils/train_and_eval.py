@@ -17,6 +17,7 @@ from torch.amp import autocast
 
 from unetseg_hip import losses
 from unetseg_hip.boundary import Accumulator as BoundaryAccumulator, labels_from_logits
+from unetseg_hip.curve import Accumulator as CurveAccumulator
 from unetseg_hip.skeleton import Accumulator as SkeletonAccumulator
 from utils.utils import get_lr
 
@@ -182,17 +183,30 @@ def _add_counts(accs, logits, targets):
             a.add(pred, targets)
 
 
+def _curve_acc(curve, ignore_index=None):
+    """the score-histogram accumulator of an evaluation loop, or None; a CurveAccumulator is taken as it is, so
+    the caller can read its table after the loop"""
+    if curve is None or isinstance(curve, CurveAccumulator):
+        return curve
+    return CurveAccumulator(curve, ignore_index)
+
+
 def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignore_index=None, max_batches=None,
-                    boundary=None, skeleton=None, boundary_weight=0.0, boundary_normalize=True, cldice_weight=0.0,
-                    cldice_iters=3):
+                    boundary=None, skeleton=None, curve=None, boundary_weight=0.0, boundary_normalize=True,
+                    cldice_weight=0.0, cldice_iters=3):
     """train_and_eval.py:266-305: eval-mode fp32 forward, global tp/fp/fn/tn, metrics with eps 1e-7.
     boundary_weight, cldice_weight: the training objective's extra terms, so the reported loss is that objective.
     boundary: None, or {"tolerance": px, "biou_d": px or None} to add the boundary metrics of class 1
     (unetseg_hip/boundary.py), counted on the device and read with the confusion counts.
     skeleton: None, or {"max_passes": int or None} to add clDice, Skeleton Precision and Skeleton Recall of class 1
-    on hard skeletons (unetseg_hip/skeleton.py), counted on the device and pooled over the split."""
+    on hard skeletons (unetseg_hip/skeleton.py), counted on the device and pooled over the split.
+    curve: None, or {"bins": K, "ece_bins": M, "threshold": t or None} (or a unetseg_hip.curve.Accumulator built
+    from such options) to add the operating-point and calibration keys (unetseg_hip/curve.py: Best Threshold /
+    IoU / F1, IoU@0.5, AP, AUROC, ECE, and the four @T keys with a threshold) from a score histogram counted on
+    the device."""
     model_eval = model.eval().to(device)
     accs = _metric_accs(boundary, skeleton, (1,), ignore_index)
+    cacc = _curve_acc(curve, ignore_index)
     total_loss = torch.zeros((), dtype=torch.float64, device=device)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     seen_batches = 0
@@ -205,6 +219,8 @@ def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignor
             total_loss += loss
             losses.binary_confusion(outputs, pngs, conf, ignore_index)
             _add_counts(accs, outputs, pngs)
+            if cacc is not None:
+                cacc.add(outputs, pngs)
             seen_batches += 1
             if max_batches is not None and seen_batches >= max_batches:
                 break
@@ -213,6 +229,8 @@ def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignor
     metrics["Loss"] = float(total_loss.item() / max(seen_batches, 1))
     for a in accs:
         metrics.update(a.metrics())
+    if cacc is not None:
+        metrics.update(cacc.metrics())
     return metrics
 
 
@@ -253,12 +271,13 @@ def train_one_epoch_multitask(model, optimizer, train_loader, device, criterion,
     return l, sl, cl, 100.0 * float(correct.item()) / max(total, 1)
 
 
-def evaluate_multitask(model, loader, device, criterion, max_batches=None, boundary=None, skeleton=None):
+def evaluate_multitask(model, loader, device, criterion, max_batches=None, boundary=None, skeleton=None, curve=None):
     """train.py:294-355 / val.py:73-110: eval-mode forward; seg IoU = I/(U+1e-6), Dice = 2I/(|P|+|T|+1e-6)
     with P = sigmoid(seg) > 0.5 (fused confusion kernel, u64 counts on the device); cls accuracy %.
-    boundary, skeleton: as in evaluate_binary, on the segmentation head."""
+    boundary, skeleton, curve: as in evaluate_binary, on the segmentation head."""
     model.eval()
     accs = _metric_accs(boundary, skeleton)
+    cacc = _curve_acc(curve)
     sums = torch.zeros(3, dtype=torch.float64, device=device)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     correct = torch.zeros((), dtype=torch.int64, device=device)
@@ -274,6 +293,8 @@ def evaluate_multitask(model, loader, device, criterion, max_batches=None, bound
             sums += torch.stack([loss, seg_loss, cls_loss]).double()
             losses.binary_confusion(seg_logits, seg_targets, conf)
             _add_counts(accs, seg_logits, seg_targets)
+            if cacc is not None:
+                cacc.add(seg_logits, seg_targets)
             correct += cls_logits.argmax(1).eq(cls_targets).sum()
             total += cls_targets.size(0)
     tp, fp, fn, _tn = (float(v) for v in conf.tolist())
@@ -285,6 +306,8 @@ def evaluate_multitask(model, loader, device, criterion, max_batches=None, bound
                "Cls Acc": 100.0 * float(correct.item()) / max(total, 1)}
     for a in accs:
         metrics.update(a.metrics())
+    if cacc is not None:
+        metrics.update(cacc.metrics())
     return metrics
 
 

@@ -12,6 +12,12 @@ IoU at `--boundary-iou-d` pixels and HD95 (unetseg_hip/boundary.py), printed aft
 `--skeleton-metrics` adds clDice, Skeleton Precision and Skeleton Recall on hard skeletons
 (unetseg_hip/skeleton.py; `--skeleton-max-passes` caps the thinning passes), printed after those.
 
+`--curve-metrics` (binary and multitask) adds the operating-point and calibration keys of
+unetseg_hip/curve.py from a score histogram of `--curve-bins` bins counted on the device: the best-IoU
+threshold with its IoU and F1, IoU at 0.5, AP, AUROC and ECE, and with `--threshold T` the IoU / F1 /
+precision / recall at T.  It writes `curve.csv` (the confusion counts at every threshold) and
+`threshold.json` into `--curve-out` (default: the experiment folder that holds the weights).
+
 `--tta MODE` evaluates the model under flip / quarter-turn test-time augmentation
 (unetseg_hip/tta.py): the metrics and the reported loss are then computed on the merged
 log-probabilities, which stand in for the logits.
@@ -33,6 +39,7 @@ from model.model_factory import SUPPORTED_MODELS, build_model  # noqa: E402
 from unetseg_hip import losses  # noqa: E402
 from unetseg_hip.boundary import KEYS as BOUNDARY_KEYS, Accumulator as BoundaryAccumulator  # noqa: E402
 from unetseg_hip.boundary import labels_from_logits  # noqa: E402
+from unetseg_hip import curve as curve_mod  # noqa: E402
 from unetseg_hip.skeleton import KEYS as SKELETON_KEYS, Accumulator as SkeletonAccumulator  # noqa: E402
 from unetseg_hip.tta import MODES as TTA_MODES, TTA  # noqa: E402
 from utils.hf_dataloader import DeviceLoader, HFUnetDataset, make_collate  # noqa: E402
@@ -67,9 +74,37 @@ def print_skeleton(m):
     print("\t".join(f"{m[k]:.4f}" for k in SKELETON_KEYS))
 
 
+def curve_accumulator(args):
+    """the `curve` argument of the evaluate loops from the flags; None without --curve-metrics"""
+    if not args.curve_metrics:
+        return None
+    return curve_mod.Accumulator({"bins": args.curve_bins, "threshold": args.threshold})
+
+
+def curve_folder(args):
+    """--curve-out, or the experiment folder of the weights (the parent of their `weights` folder), or the
+    folder the weights lie in"""
+    if args.curve_out:
+        return args.curve_out
+    d = os.path.dirname(os.path.abspath(args.weights))
+    return os.path.dirname(d) if os.path.basename(d) == "weights" else d
+
+
+def report_curve(args, cacc, m):
+    """print the curve keys and write curve.csv and threshold.json"""
+    keys = curve_mod.KEYS + (curve_mod.KEYS_AT if args.threshold is not None else ())
+    print("\t".join(f"{LogColor.RED}{k}{LogColor.RESET}" for k in keys))
+    print("\t".join(f"{m[k]:.4f}" for k in keys))
+    folder = curve_folder(args)
+    os.makedirs(folder, exist_ok=True)
+    curve_mod.write_csv(os.path.join(folder, "curve.csv"), cacc.table())
+    curve_mod.write_threshold(os.path.join(folder, "threshold.json"), m, cacc.K)
+
+
 def val(args):
     boundary = boundary_options(args)
     skeleton = skeleton_options(args)
+    cacc = curve_accumulator(args)
     num_classes = args.num_classes + 1 if args.task == "multiclass" else 2  # val.py:22-27
     device = torch.device(args.device)
     input_shape = [args.input_size] * 2
@@ -100,7 +135,7 @@ def val(args):
         m = evaluate_binary(model, loader, device, loss_name=args.loss, pos_weight=None, ignore_index=None,
                             boundary=boundary, boundary_weight=args.boundary_loss_weight,
                             boundary_normalize=not args.boundary_loss_pixels, cldice_weight=args.cldice_weight,
-                            cldice_iters=args.cldice_iters, skeleton=skeleton)
+                            cldice_iters=args.cldice_iters, skeleton=skeleton, curve=cacc)
         print(f"{LogColor.RED}Dice{LogColor.RESET}\t{LogColor.RED}IoU{LogColor.RESET}\t{LogColor.RED}Precision"
               f"{LogColor.RESET}\t{LogColor.RED}Recall{LogColor.RESET}\t{LogColor.RED}Accuracy{LogColor.RESET}")
         print(f"{m['Dice']:.4f}\t{m['IoU']:.4f}\t{m['Precision']:.4f}\t{m['Recall']:.4f}\t{m['Accuracy']:.4f}")
@@ -108,6 +143,8 @@ def val(args):
             print_boundary(m)
         if skeleton is not None:
             print_skeleton(m)
+        if cacc is not None:
+            report_curve(args, cacc, m)
         return m
     if args.task == "multiclass":
         m = evaluate(model, loader, device, dice_loss=True, focal_loss=False, num_classes=num_classes,
@@ -134,6 +171,8 @@ def val(args):
                 for acc_ in (bacc, sacc):
                     if acc_ is not None:
                         acc_.add(seg_pred, seg_t)
+            if cacc is not None:
+                cacc.add(seg_logits, seg_t)
             pred = cls_logits.argmax(1)
             for c in range(3):
                 sel = cls_t == c
@@ -158,6 +197,9 @@ def val(args):
     if sacc is not None:
         m.update(sacc.metrics())
         print_skeleton(m)
+    if cacc is not None:
+        m.update(cacc.metrics())
+        report_curve(args, cacc, m)
     return m
 
 
@@ -196,6 +238,17 @@ def parse_args(argv=None):
     p.add_argument("--skeleton-max-passes", default=None, type=int,
                    help="cap of the thinning passes; default min(H, W) // 2 + 8.  An image still losing pixels at the "
                         "cap is an error, not a silently wrong score")
+    p.add_argument("--curve-metrics", action="store_true",
+                   help="also report the best-IoU threshold with its IoU and F1, IoU at 0.5, AP, AUROC and ECE from a "
+                        "score histogram, and write curve.csv and threshold.json (--task binary and multitask)")
+    p.add_argument("--curve-bins", default=1000, type=int,
+                   help="bins K of the score histogram (even, a multiple of 10, at most 4096); threshold k stands for "
+                        "probability k / K")
+    p.add_argument("--threshold", default=None, type=float,
+                   help="with --curve-metrics: also report IoU / F1 / precision / recall at this probability "
+                        "threshold, a multiple of 1 / --curve-bins")
+    p.add_argument("--curve-out", default="",
+                   help="folder of curve.csv and threshold.json; default: the experiment folder that holds --weights")
     p.add_argument("--boundary-loss-weight", default=0.0, type=float,
                    help="the training run's boundary-loss weight, so the reported loss (m['Loss'], --task binary) is "
                         "that objective; the multitask evaluation reports no loss")
@@ -207,6 +260,15 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.skeleton_max_passes is not None and args.skeleton_max_passes < 0:
         p.error("--skeleton-max-passes must be >= 0")
+    if args.curve_metrics:
+        if args.task == "multiclass":
+            p.error("--curve-metrics needs --task binary or multitask (one-vs-rest softmax scores are out of scope)")
+        try:
+            curve_mod.Accumulator({"bins": args.curve_bins, "threshold": args.threshold})
+        except ValueError as e:
+            p.error(f"--curve-bins / --threshold: {e}")
+    elif args.threshold is not None:
+        p.error("--threshold needs --curve-metrics")
     check_loss_term_args(p, args)
     return args
 
