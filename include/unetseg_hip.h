@@ -85,7 +85,11 @@ int unetseg_conv_tile_m(void);
 int unetseg_conv2d_fwd_tile_m(int dtype, int c1, int ldc1, int c2, int ldc2, int n, int h, int w, int cout, int r,
                               int s, int stride, int pad);
 /* y[n,p,q,cout] = conv(cat(x1[.., c1], x2[.., c2]), wk) (+bias) (ReLU); stats (may be NULL):
- * fp32 [ceil(M/tile)][2][cout] = per-tile (sum, M2 about the tile mean) of the rounded y (BN train) */
+ * fp32 [ceil(M/tile)][2][cout] = per-tile (sum, M2 about the tile mean) of the rounded y (BN train).
+ * Tile g holds output rows [g * tile, (g + 1) * tile) (the last one ragged) on the TN tiles, the gather rings and
+ * the generic kernel; on halo3, first3x3 and the halo-A rings it is the g-th (tile / 32) x 32 spatial block, dealt
+ * row-major over (image, block row, block column).  The sum is exact whenever the tile's |y| sum to less than
+ * 2^24 (tests/test_gpu_conv_fast_exact.py holds every configuration to it per tile). */
 int unetseg_conv2d_fwd(int dtype, const void* x1, int c1, int ldc1, const void* x2, int c2, int ldc2, int n, int h,
                        int w, const void* wk, int cout, int r, int s, int stride, int pad, const float* bias, int relu,
                        void* y, int ldy, float* stats, void* stream);
@@ -141,7 +145,14 @@ int unetseg_conv2d_dgrad_config(int dtype, int ldy, int n, int p, int q, int cou
  * slabs (reduced by wgrad_reduce<16> from 16 slabs, <4> from 4, else <1>) */
 int unetseg_conv2d_wgrad_config(int dtype, int c1, int ldc1, int c2, int ldc2, int n, int h, int w, int ldy, int cout,
                                 int r, int s, int stride, int pad, int* splits_out);
-/* dx[n,h,w,cin] (+)= conv_transpose(dy[n,p,q,cout], wt) */
+/* dx[n,h,w,cin] (+)= conv_transpose(dy[n,p,q,cout], wt).  The gradient g is accumulated in fp32; accumulate == 0
+ * stores bf16(g).  Rounding of accumulate != 0 in bf16, by kernel family (asserted per configuration, bit for bit,
+ * by tests/test_gpu_conv_fast_exact.py):
+ *   halo3 (the 64-channel 3x3 kernel)                           dx = bf16(g + dx): one rounding;
+ *   every TN configuration (tiles, gather rings, halo-A rings,  dx = bf16(bf16(g) + dx): the epilogue rounds g as
+ *   their persistent forms, the merged stride-2 classes)        the plain store would, then adds -- two roundings,
+ *                                                               what autograd's accumulation of two bf16 tensors gives;
+ *   the generic kernel                                          dx = bf16(g + dx), fp32: dx = g + dx. */
 int unetseg_conv2d_dgrad(int dtype, const void* dy, int ldy, int n, int p, int q, const void* wt, int cout, int cin,
                          int r, int s, int stride, int pad, void* dx, int ldx, int h, int w, int accumulate,
                          void* stream);
@@ -159,8 +170,10 @@ int unetseg_conv2d_dgrad_post(int dtype, const void* dy, int ldy, int n, int p, 
 /* 1x1 stride-1 data gradient accumulated onto the other consumers' gradient already in dx (pixel stride
    ldx >= cin, a multiple of 8: dx may be a channel slice of a skip-concat gradient), with the residual
    BN-add-ReLU backward's first pass in its epilogue (model/resnet_backbone.py:88,110-113: the next
-   block's conv1 is the last consumer of the block output): dx = mask * bf16(dgrad + dx), mask =
-   the packed ReLU bits written by unetseg_bn_apply_mask, part[rows][2 or 3][cin] = (sum d,
+   block's conv1 is the last consumer of the block output): dx = d = mask * bf16(bf16(dgrad) + dx) -- the
+   TN rule of unetseg_conv2d_dgrad: the gradient is rounded to bf16, then added to the old value in fp32
+   and rounded again, bit for bit what the accumulating unetseg_conv2d_dgrad followed by the mask stores --
+   mask = the packed ReLU bits written by unetseg_bn_apply_mask, part[rows][2 or 3][cin] = (sum d,
    sum d * (y1 - mean1) * inv1 [, sum d * (y2 - mean2) * inv2]) per row tile (y2 = the downsample
    branch's BN input, NULL: none).  Replaces unetseg_bn_bwd_reduce over dx.  part == NULL: returns rows,
    or 0 when the shape has no fused kernel (bf16 only). */
