@@ -745,6 +745,20 @@ int unetseg_adam(float* p, const float* g, float* m, float* v, long n, float lr,
    update) are read from device memory */
 int unetseg_adam_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, float beta1,
                      float beta2, float eps, float wd, const float* grad_scale, void* stream);
+/* Adam fused with an exponential moving average of the weights: the step of unetseg_adam (p, m, v bit-identical to
+   it) and, in the same pass, ema = ema + one_minus_decay * (p_new - ema).  one_minus_decay in [0, 1]: the host
+   forms 1 - d_t in double and rounds it once.  Any 4-byte-aligned slices; n == 0 launches nothing. */
+int unetseg_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float beta1,
+                     float beta2, float eps, float wd, int step, float one_minus_decay, const float* grad_scale,
+                     void* stream);
+/* the capturable form: 1 - d_t is formed in the kernel, in double, from the device step count t = *step + 1, with
+   d_t = min(decay, (1 + t) / (10 + t)) when warmup != 0 and d_t = decay otherwise; then *step advances as in
+   unetseg_adam_dev */
+int unetseg_adam_ema_dev(float* p, const float* g, float* m, float* v, float* ema, long n, const float* hyper,
+                         int* step, float beta1, float beta2, float eps, float wd, float decay, int warmup,
+                         const float* grad_scale, void* stream);
+/* exchanges two fp32 arrays in place, bit for bit (a and b must not overlap) */
+int unetseg_swap_f32(float* a, float* b, long n, void* stream);
 
 #ifdef __cplusplus
 }

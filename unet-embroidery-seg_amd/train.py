@@ -18,6 +18,7 @@ and multitask.  Differences, all deliberate:
 from __future__ import annotations
 
 import argparse
+import contextlib
 import csv
 import datetime
 import json
@@ -67,14 +68,16 @@ def create_model(model_name, num_classes, weights, num_seg_classes=1, num_cls_cl
     return model
 
 
-def get_optimizer_and_lr(model, batch_size, train_epoch, momentum, weight_decay):
+def get_optimizer_and_lr(model, batch_size, train_epoch, momentum, weight_decay, ema_decay=0.0, ema_warmup=True):
     """train.py:62-78: Adam(lr clamped to 1e-4, betas (momentum, 0.999), coupled wd) + warm-cos per epoch.
-    The optimizer is FusedAdam: one HIP launch over the model's flat parameter arena, same update."""
+    The optimizer is FusedAdam: one HIP launch over the model's flat parameter arena, same update; with
+    ema_decay > 0 the same launch keeps the weight average (--ema-decay)."""
     init_lr, min_lr, nbs = 1e-4, 1e-6, 16
     lim_max = lim_min = 1e-4
     init_fit = min(max(batch_size / nbs * init_lr, lim_min), lim_max)
     min_fit = min(max(batch_size / nbs * min_lr, lim_min * 1e-2), lim_max * 1e-2)
-    optimizer = FusedAdam(model, lr=init_fit, betas=(momentum, 0.999), weight_decay=weight_decay)
+    optimizer = FusedAdam(model, lr=init_fit, betas=(momentum, 0.999), weight_decay=weight_decay,
+                          ema_decay=ema_decay, ema_warmup=ema_warmup)
     return optimizer, get_lr_scheduler("cos", init_fit, min_fit, train_epoch)
 
 
@@ -161,7 +164,8 @@ def train(args):
     model = model.to(device)
     buckets = GradBuckets(model) if world > 1 else None  # broadcasts rank 0's weights
     scaler = torch.amp.GradScaler(device.type, enabled=args.amp)
-    optimizer, lr_fn = get_optimizer_and_lr(model, args.batch_size, args.epochs, args.momentum, args.weight_decay)
+    optimizer, lr_fn = get_optimizer_and_lr(model, args.batch_size, args.epochs, args.momentum, args.weight_decay,
+                                            ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup)
 
     pos_weight = None
     if args.task == "binary" and args.loss == "bce" and args.pos_weight:
@@ -183,6 +187,8 @@ def train(args):
     mvb = args.max_val_batches or None
     best_score, best_epoch, best_metrics = -1.0, None, None
     best_path, last_path = os.path.join(weights_folder, "best.pth"), os.path.join(weights_folder, "last.pth")
+    last_raw_path = os.path.join(weights_folder, "last_raw.pth")  # --ema-decay: the live (not averaged) weights
+    averaged = optimizer.averaged if args.ema_decay > 0 else contextlib.nullcontext
     # the clDice metric of the validation and test passes (model selection stays on IoU / Mean IoU)
     skel = {"max_passes": args.skeleton_max_passes} if args.skeleton_metrics else None
     # the operating-point and calibration keys of the binary head (unetseg_hip/curve.py), the same way
@@ -214,27 +220,33 @@ def train(args):
             buckets.sync_buffers()  # BN running statistics: rank 0's (DDP broadcast_buffers semantics)
         if rank != 0:
             continue
-        if args.task == "multitask":
-            metrics = evaluate_multitask(model, val_loader, device, criterion, mvb, skeleton=skel, curve=crv)
-            print(f"Val - IoU: {metrics['IoU']:.4f}, Dice: {metrics['Dice']:.4f}, Cls Acc: {metrics['Cls Acc']:.2f}%")
-            score = float(metrics["IoU"])
-        elif args.task == "binary":
-            metrics = evaluate_binary(model, val_loader, device, loss_name=args.loss, pos_weight=pos_weight,
-                                      ignore_index=None, max_batches=mvb, skeleton=skel, curve=crv, **bnd)
-            score = float(metrics["IoU"])
-        else:
-            metrics = evaluate(model, val_loader, device, args.use_dice, args.loss == "focal", num_classes,
-                               lovasz_softmax=args.loss == "lovasz_softmax", skeleton=skel)
-            score = float(metrics["Mean IoU"])
-        val_losses.append(metrics["Loss"])
-        history.append(metrics)
-        if score > best_score:
-            best_score, best_epoch, best_metrics = score, epoch + 1, metrics
-            torch.save(model.state_dict(), best_path)
-            print(f"New best model saved with score: {best_score:.4f}")
-            if crv is not None:  # the operating point of the kept checkpoint, from the validation split only
-                write_threshold(os.path.join(exp_folder, "threshold.json"), metrics, args.curve_bins)
-        torch.save(model.state_dict(), last_path)
+        # with --ema-decay the averaged weights are validated, selected on and saved; the live ones are swapped back
+        # before the next epoch trains (BatchNorm statistics are the live ones either way)
+        with averaged():
+            if args.task == "multitask":
+                metrics = evaluate_multitask(model, val_loader, device, criterion, mvb, skeleton=skel, curve=crv)
+                print(f"Val - IoU: {metrics['IoU']:.4f}, Dice: {metrics['Dice']:.4f}, "
+                      f"Cls Acc: {metrics['Cls Acc']:.2f}%")
+                score = float(metrics["IoU"])
+            elif args.task == "binary":
+                metrics = evaluate_binary(model, val_loader, device, loss_name=args.loss, pos_weight=pos_weight,
+                                          ignore_index=None, max_batches=mvb, skeleton=skel, curve=crv, **bnd)
+                score = float(metrics["IoU"])
+            else:
+                metrics = evaluate(model, val_loader, device, args.use_dice, args.loss == "focal", num_classes,
+                                   lovasz_softmax=args.loss == "lovasz_softmax", skeleton=skel)
+                score = float(metrics["Mean IoU"])
+            val_losses.append(metrics["Loss"])
+            history.append(metrics)
+            if score > best_score:
+                best_score, best_epoch, best_metrics = score, epoch + 1, metrics
+                torch.save(model.state_dict(), best_path)
+                print(f"New best model saved with score: {best_score:.4f}")
+                if crv is not None:  # the operating point of the kept checkpoint, from the validation split only
+                    write_threshold(os.path.join(exp_folder, "threshold.json"), metrics, args.curve_bins)
+            torch.save(model.state_dict(), last_path)
+        if args.ema_decay > 0:
+            torch.save(model.state_dict(), last_raw_path)  # the live weights, e.g. to resume from
 
     if rank == 0:
         print(f"Training completed in {datetime.timedelta(seconds=int(time.time() - t0))}")
@@ -331,6 +343,13 @@ def parse_args(argv=None):
     p.add_argument("--lr", default=0.0001, type=float)
     p.add_argument("--momentum", default=0.9, type=float)
     p.add_argument("--wd", "--weight-decay", default=1e-4, type=float, dest="weight_decay")
+    p.add_argument("--ema-decay", default=0.0, type=float,
+                   help="decay of an exponential moving average of the weights kept by the Adam kernel (0 = off); "
+                        "validation, model selection, best.pth, last.pth, the test pass and the visual export then "
+                        "use the averaged weights and last_raw.pth holds the live ones; BatchNorm statistics are "
+                        "not averaged")
+    p.add_argument("--no-ema-warmup", action="store_true",
+                   help="use --ema-decay from the first step instead of min(decay, (1 + t) / (10 + t))")
     p.add_argument("--amp", action=argparse.BooleanOptionalAction, default=True)
     p.add_argument("--seed", default=11, type=int)
     p.add_argument("--cache-dir", default=".hf-cache/datasets")
@@ -345,6 +364,8 @@ def parse_args(argv=None):
     p.add_argument("--out-dir", default="logs")
     args = p.parse_args(argv)
     check_loss_term_args(p, args)
+    if not 0.0 <= args.ema_decay < 1.0:
+        p.error("--ema-decay must be in [0, 1)")
     if args.skeleton_max_passes is not None and args.skeleton_max_passes < 0:
         p.error("--skeleton-max-passes must be >= 0")
     if args.curve_metrics:

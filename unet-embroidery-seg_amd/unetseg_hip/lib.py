@@ -155,6 +155,9 @@ SIGNATURES = {
     "unetseg_skel_counts": (I, [P, P, P, P, P, P, I, I, I, I, I, P, P]),
     "unetseg_curve_max_bins": (I, []),
     "unetseg_curve_hist": (I, [P, I, P, I, L, L, P, I, P, P]),
+    "unetseg_adam_ema": (I, [P, P, P, P, P, L, F, F, F, F, F, I, F, P, P]),
+    "unetseg_adam_ema_dev": (I, [P, P, P, P, P, L, P, P, F, F, F, F, F, I, P, P]),
+    "unetseg_swap_f32": (I, [P, P, L, P]),
 }
 
 #: functions returning a value rather than a status (no RuntimeError on non-zero)
