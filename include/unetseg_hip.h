@@ -271,7 +271,8 @@ int unetseg_colsum_finalize(const float* part, int C, int G, float* out, int acc
 int unetseg_bn_bwd_finalize_rows(const float* part, int C, int G, long M, const float* g1, const float* inv1,
                                  float* dg1, float* db1, float* coef, void* stream);
 /* the same for the residual post-op's part[G][1+nbranch][C] (unetseg_conv2d_dgrad_post_res): coefficients
-   of both branches as unetseg_bn_bwd_finalize */
+   of both branches as unetseg_bn_bwd_finalize, coef [3*nbranch][C].  nbranch == 1: g2, inv2, dg2, db2 may be NULL
+   and only coef rows 0..2 are written; nbranch == 2: db2 and coef[4] take the same sum of dz as db1 and coef[1] */
 int unetseg_bn_bwd_finalize_rows_res(const float* part, int C, int G, long M, int nbranch, const float* g1,
                                      const float* inv1, float* dg1, float* db1, const float* g2, const float* inv2,
                                      float* dg2, float* db2, float* coef, void* stream);
