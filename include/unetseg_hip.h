@@ -683,6 +683,44 @@ int unetseg_curve_hist(const float* out, int nch, const int64_t* tgt, int B, lon
                        const float* edges /* [K - 1] */, int K, unsigned long long* hist /* [2][K], accumulates */,
                        void* stream);
 
+/* ---- object-level agreement of two class maps: Panoptic Quality, object F1, splits and merges (no
+ * ---- reference counterpart; unetseg_hip/objects.py) ------------------------------------------------
+ * pred, target int32 [N][H][W] (the caller sets the pixels outside the domain to 0 in both).  For a class c in
+ * 1 .. 255 an object is a connected component of class c (unetseg_ccl_label at `connectivity`), named by its
+ * root; a predicted object p and a target object g overlap when some pixel has pred == c, target == c,
+ * root_pred == p and root_target == g; inter(p, g) is the number of such pixels and union = area_p + area_g -
+ * inter.  The three stages share a workspace of unetseg_objects_workspace(N, H, W) bytes, 16-byte aligned:
+ *   unetseg_objects_label: roots and stats of both maps (the ccl entry points), once per pair of maps;
+ *   unetseg_objects_pairs: the table of the overlapping pairs of class c with their inter, one open-addressing
+ *     table per image of cap = the smallest power of two >= max(H W, 2) slots (at most ceil(H W / 2) pairs are
+ *     distinct: csrc/objects.hip).  aggregate != 0 gathers a block's runs in LDS first (the product path);
+ *     0 sends every run to the table (the timing tool's comparison);
+ *   unetseg_objects_match: out int64 [20] += from that table
+ *     [0] target objects                       [1] predicted objects
+ *     [2] target objects with >= 1 partner     [3] predicted objects with >= 1 partner
+ *     [4] target objects with >= 2 (splits)    [5] predicted objects with >= 2 (merges)
+ *     [6 + j], j = 0 .. 9: the pairs with 20 inter > (10 + j) union (IoU > 0.5, 0.55, .. 0.95), 64-bit integers
+ *     [16] the sum over the pairs with 2 inter > union of floor(inter 2^32 / union), unsigned 64-bit
+ *     [17] distinct overlapping pairs          [18] table insertions that found no slot (0 unless there is a bug)
+ *     [19] N
+ * All integer, integer atomics only, bitwise reproducible, on the caller's stream without a host wait; the number
+ * of launches depends on the shape only.  Checked before any launch: null pointers, N, H, W >= 0, H W <= 2^31 - 1,
+ * N H W <= 2^40, connectivity 4 or 8, 1 <= c <= 255, ws_bytes and the alignment of ws.  An empty batch
+ * (N H W == 0) launches nothing and returns 0; the workspace query returns 0 for it and for a refused shape. */
+/* host only: the pair kernel gathers the runs of a tile of *tw x *th pixels per block */
+int unetseg_objects_tile(int* tw, int* th);
+size_t unetseg_objects_workspace(int N, int H, int W); /* host only */
+/* host only: at[0 .. 5) = byte offsets in the workspace of roots int32 [2][N][H][W], stats int32 [2][4][N][H][W],
+ * keys u64 [N][cap] ((root_pred << 32) | root_target, all ones = empty), inter u32 [N][cap], degrees int32
+ * [2][N][H][W] (pred before target); at[5] = cap */
+int unetseg_objects_layout(int N, int H, int W, int64_t* at /* [6] */);
+int unetseg_objects_label(const int32_t* pred, const int32_t* target, int N, int H, int W, int connectivity, void* ws,
+                          size_t ws_bytes, void* stream);
+int unetseg_objects_pairs(const int32_t* pred, const int32_t* target, int N, int H, int W, int c, int aggregate,
+                          void* ws, size_t ws_bytes, void* stream);
+int unetseg_objects_match(const int32_t* pred, const int32_t* target, int N, int H, int W, int c,
+                          int64_t* out /* [20], accumulates */, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- device augmentation of the loader (utils/hf_dataloader.py:67-105, 111-180, 183-213) -------
  * Replaces HFUnetDataset.get_random_data + preprocess + hf_unet_dataset_collate for one batch:
  * PIL BICUBIC image / NEAREST mask resize (bit-exact), flip, paste on the grey / zero canvas,

@@ -193,6 +193,8 @@ def train(args):
     skel = {"max_passes": args.skeleton_max_passes} if args.skeleton_metrics else None
     # the operating-point and calibration keys of the binary head (unetseg_hip/curve.py), the same way
     crv = {"bins": args.curve_bins} if args.curve_metrics else None
+    # the object-level keys (unetseg_hip/objects.py: PQ, object F1, split and merge rates), the same way
+    obj = {"connectivity": args.object_connectivity, "min_area": args.object_min_area} if args.object_metrics else None
     train_losses, val_losses, history = [], [], []
     t0 = time.time()
     for epoch in range(args.epochs):
@@ -224,17 +226,19 @@ def train(args):
         # before the next epoch trains (BatchNorm statistics are the live ones either way)
         with averaged():
             if args.task == "multitask":
-                metrics = evaluate_multitask(model, val_loader, device, criterion, mvb, skeleton=skel, curve=crv)
+                metrics = evaluate_multitask(model, val_loader, device, criterion, mvb, skeleton=skel, curve=crv,
+                                             objects=obj)
                 print(f"Val - IoU: {metrics['IoU']:.4f}, Dice: {metrics['Dice']:.4f}, "
                       f"Cls Acc: {metrics['Cls Acc']:.2f}%")
                 score = float(metrics["IoU"])
             elif args.task == "binary":
                 metrics = evaluate_binary(model, val_loader, device, loss_name=args.loss, pos_weight=pos_weight,
-                                          ignore_index=None, max_batches=mvb, skeleton=skel, curve=crv, **bnd)
+                                          ignore_index=None, max_batches=mvb, skeleton=skel, curve=crv, objects=obj,
+                                          **bnd)
                 score = float(metrics["IoU"])
             else:
                 metrics = evaluate(model, val_loader, device, args.use_dice, args.loss == "focal", num_classes,
-                                   lovasz_softmax=args.loss == "lovasz_softmax", skeleton=skel)
+                                   lovasz_softmax=args.loss == "lovasz_softmax", skeleton=skel, objects=obj)
                 score = float(metrics["Mean IoU"])
             val_losses.append(metrics["Loss"])
             history.append(metrics)
@@ -265,13 +269,14 @@ def train(args):
                 pass
             elif args.task == "multitask":
                 test_metrics = evaluate_multitask(model, test_loader, device, criterion, mtest, skeleton=skel,
-                                                  curve=crv)
+                                                  curve=crv, objects=obj)
             elif args.task == "multiclass":
-                test_metrics = evaluate(model, test_loader, device, True, False, num_classes, skeleton=skel)
+                test_metrics = evaluate(model, test_loader, device, True, False, num_classes, skeleton=skel,
+                                        objects=obj)
             else:
                 test_metrics = evaluate_binary(model, test_loader, device, loss_name=args.loss, pos_weight=pos_weight,
                                                ignore_index=None, max_batches=mtest, skeleton=skel, curve=crv,
-                                               **bnd)
+                                               objects=obj, **bnd)
             with open(os.path.join(exp_folder, "test_metrics.json"), "w", encoding="utf-8") as f:
                 json.dump(test_metrics, f, ensure_ascii=False, indent=2)
             # fixed-sample visual export of the test split (train.py:476-486; HF datasets only)
@@ -331,6 +336,15 @@ def parse_args(argv=None):
                         "threshold.json holds the best epoch's validation threshold; model selection stays on IoU")
     p.add_argument("--curve-bins", default=1000, type=int,
                    help="bins K of the score histogram (even, a multiple of 10, at most 4096)")
+    p.add_argument("--object-metrics", action="store_true",
+                   help="validation and test also report PQ, SQ, Object F1 / Precision / Recall, Object F1@[.5:.95], "
+                        "Detection Recall, False Object Rate, Split Rate and Merge Rate of the connected components "
+                        "(into the metric history); model selection stays on IoU / Mean IoU")
+    p.add_argument("--object-connectivity", default=8, type=int, choices=[4, 8],
+                   help="connectivity of the objects of --object-metrics")
+    p.add_argument("--object-min-area", default=0, type=int,
+                   help="with --object-metrics: drop predicted components below this area first, as predict.py "
+                        "--min-area does")
     p.add_argument("--pos-weight", default="auto")
     p.add_argument("--pos-weight-samples", default=80, type=int)
     p.add_argument("--use-dice", action=argparse.BooleanOptionalAction, default=True)
@@ -368,6 +382,8 @@ def parse_args(argv=None):
         p.error("--ema-decay must be in [0, 1)")
     if args.skeleton_max_passes is not None and args.skeleton_max_passes < 0:
         p.error("--skeleton-max-passes must be >= 0")
+    if args.object_min_area < 0:
+        p.error("--object-min-area must be >= 0")
     if args.curve_metrics:
         if args.task == "multiclass":
             p.error("--curve-metrics needs --task binary or multitask (one-vs-rest softmax scores are out of scope)")

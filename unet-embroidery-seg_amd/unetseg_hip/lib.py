@@ -155,6 +155,12 @@ SIGNATURES = {
     "unetseg_skel_counts": (I, [P, P, P, P, P, P, I, I, I, I, I, P, P]),
     "unetseg_curve_max_bins": (I, []),
     "unetseg_curve_hist": (I, [P, I, P, I, L, L, P, I, P, P]),
+    "unetseg_objects_tile": (I, [P, P]),
+    "unetseg_objects_workspace": (SZ, [I, I, I]),
+    "unetseg_objects_layout": (I, [I, I, I, P]),
+    "unetseg_objects_label": (I, [P, P, I, I, I, I, P, SZ, P]),
+    "unetseg_objects_pairs": (I, [P, P, I, I, I, I, I, P, SZ, P]),
+    "unetseg_objects_match": (I, [P, P, I, I, I, I, P, P, SZ, P]),
     "unetseg_adam_ema": (I, [P, P, P, P, P, L, F, F, F, F, F, I, F, P, P]),
     "unetseg_adam_ema_dev": (I, [P, P, P, P, P, L, P, P, F, F, F, F, F, I, P, P]),
     "unetseg_swap_f32": (I, [P, P, L, P]),

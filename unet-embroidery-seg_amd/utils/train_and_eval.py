@@ -18,6 +18,7 @@ from torch.amp import autocast
 from unetseg_hip import losses
 from unetseg_hip.boundary import Accumulator as BoundaryAccumulator, labels_from_logits
 from unetseg_hip.curve import Accumulator as CurveAccumulator
+from unetseg_hip.objects import Accumulator as ObjectsAccumulator
 from unetseg_hip.skeleton import Accumulator as SkeletonAccumulator
 from utils.utils import get_lr
 
@@ -164,14 +165,17 @@ def train_one_epoch_binary(model, optimizer, train_loader, device, loss_name: st
     return float(epoch_loss.item()) / max(seen_batches, 1)
 
 
-def _metric_accs(boundary, skeleton, classes=(1,), ignore_index=None):
+def _metric_accs(boundary, skeleton, classes=(1,), ignore_index=None, objects=None):
     """the count accumulators of an evaluation loop, in the order their keys enter the metrics: the boundary
-    counts with the `boundary` options, the skeleton counts (clDice metric) with the `skeleton` options"""
+    counts with the `boundary` options, the skeleton counts (clDice metric) with the `skeleton` options, the
+    object counts with the `objects` options"""
     accs = []
     if boundary is not None:
         accs.append(BoundaryAccumulator(boundary, classes, ignore_index))
     if skeleton is not None:
         accs.append(SkeletonAccumulator(skeleton, classes, ignore_index))
+    if objects is not None:
+        accs.append(ObjectsAccumulator(objects, classes, ignore_index))
     return accs
 
 
@@ -183,6 +187,19 @@ def _add_counts(accs, logits, targets):
             a.add(pred, targets)
 
 
+def _read_counts(metrics, accs, cacc=None):
+    """the accumulators' keys after the loop's own: boundary and skeleton, then the curve's, the objects' last"""
+    late = [a for a in accs if isinstance(a, ObjectsAccumulator)]
+    for a in accs:
+        if a not in late:
+            metrics.update(a.metrics())
+    if cacc is not None:
+        metrics.update(cacc.metrics())
+    for a in late:
+        metrics.update(a.metrics())
+    return metrics
+
+
 def _curve_acc(curve, ignore_index=None):
     """the score-histogram accumulator of an evaluation loop, or None; a CurveAccumulator is taken as it is, so
     the caller can read its table after the loop"""
@@ -192,8 +209,8 @@ def _curve_acc(curve, ignore_index=None):
 
 
 def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignore_index=None, max_batches=None,
-                    boundary=None, skeleton=None, curve=None, boundary_weight=0.0, boundary_normalize=True,
-                    cldice_weight=0.0, cldice_iters=3):
+                    boundary=None, skeleton=None, curve=None, objects=None, boundary_weight=0.0,
+                    boundary_normalize=True, cldice_weight=0.0, cldice_iters=3):
     """train_and_eval.py:266-305: eval-mode fp32 forward, global tp/fp/fn/tn, metrics with eps 1e-7.
     boundary_weight, cldice_weight: the training objective's extra terms, so the reported loss is that objective.
     boundary: None, or {"tolerance": px, "biou_d": px or None} to add the boundary metrics of class 1
@@ -203,9 +220,12 @@ def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignor
     curve: None, or {"bins": K, "ece_bins": M, "threshold": t or None} (or a unetseg_hip.curve.Accumulator built
     from such options) to add the operating-point and calibration keys (unetseg_hip/curve.py: Best Threshold /
     IoU / F1, IoU@0.5, AP, AUROC, ECE, and the four @T keys with a threshold) from a score histogram counted on
-    the device."""
+    the device.
+    objects: None, or {"connectivity": 4 or 8, "min_area": int} to add the object-level keys of class 1
+    (unetseg_hip/objects.py: PQ, SQ, Object F1 / Precision / Recall, Object F1@[.5:.95], Detection Recall, False
+    Object Rate, Split Rate, Merge Rate) from connected components labelled and paired on the device."""
     model_eval = model.eval().to(device)
-    accs = _metric_accs(boundary, skeleton, (1,), ignore_index)
+    accs = _metric_accs(boundary, skeleton, (1,), ignore_index, objects)
     cacc = _curve_acc(curve, ignore_index)
     total_loss = torch.zeros((), dtype=torch.float64, device=device)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
@@ -227,11 +247,7 @@ def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignor
     tp, fp, fn, tn = (float(v) for v in conf.tolist())
     metrics = binary_segmentation_metrics(tp, fp, fn, tn)
     metrics["Loss"] = float(total_loss.item() / max(seen_batches, 1))
-    for a in accs:
-        metrics.update(a.metrics())
-    if cacc is not None:
-        metrics.update(cacc.metrics())
-    return metrics
+    return _read_counts(metrics, accs, cacc)
 
 
 def train_one_epoch_multitask(model, optimizer, train_loader, device, criterion, scaler, amp=True, max_batches=None,
@@ -271,12 +287,13 @@ def train_one_epoch_multitask(model, optimizer, train_loader, device, criterion,
     return l, sl, cl, 100.0 * float(correct.item()) / max(total, 1)
 
 
-def evaluate_multitask(model, loader, device, criterion, max_batches=None, boundary=None, skeleton=None, curve=None):
+def evaluate_multitask(model, loader, device, criterion, max_batches=None, boundary=None, skeleton=None, curve=None,
+                       objects=None):
     """train.py:294-355 / val.py:73-110: eval-mode forward; seg IoU = I/(U+1e-6), Dice = 2I/(|P|+|T|+1e-6)
     with P = sigmoid(seg) > 0.5 (fused confusion kernel, u64 counts on the device); cls accuracy %.
-    boundary, skeleton, curve: as in evaluate_binary, on the segmentation head."""
+    boundary, skeleton, curve, objects: as in evaluate_binary, on the segmentation head."""
     model.eval()
-    accs = _metric_accs(boundary, skeleton)
+    accs = _metric_accs(boundary, skeleton, objects=objects)
     cacc = _curve_acc(curve)
     sums = torch.zeros(3, dtype=torch.float64, device=device)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
@@ -304,11 +321,7 @@ def evaluate_multitask(model, loader, device, criterion, max_batches=None, bound
     metrics = {"Loss": l, "Seg Loss": sl, "Cls Loss": cl, "IoU": tp / (tp + fp + fn + 1e-6),
                "Dice": 2 * tp / ((tp + fp) + (tp + fn) + 1e-6),
                "Cls Acc": 100.0 * float(correct.item()) / max(total, 1)}
-    for a in accs:
-        metrics.update(a.metrics())
-    if cacc is not None:
-        metrics.update(cacc.metrics())
-    return metrics
+    return _read_counts(metrics, accs, cacc)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -389,15 +402,17 @@ def train_one_epoch(model, optimizer, train_loader, device, dice_loss, focal_los
 
 
 def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lovasz_softmax=False, boundary=None,
-             skeleton=None):
+             skeleton=None, objects=None):
     """train_and_eval.py:411-513: per-batch metrics averaged over batches, as the reference does.
     boundary: None, or {"tolerance": px, "biou_d": px or None} to add the boundary metrics: counted over
     the split per class 1 .. num_classes - 1 with num_classes as the ignored target value, each key the
     mean over the classes with a target edge pixel (0.0 without one).
     skeleton: None, or {"max_passes": int or None} to add the clDice metrics in the same way: the mean over the
-    classes whose target skeleton is non-empty in the split."""
+    classes whose target skeleton is non-empty in the split.
+    objects: None, or {"connectivity": 4 or 8, "min_area": int} to add the object-level keys in the same way: the
+    mean over the classes that have a target object in the split."""
     import numpy as np
-    accs = _metric_accs(boundary, skeleton, tuple(range(1, num_classes)), num_classes)
+    accs = _metric_accs(boundary, skeleton, tuple(range(1, num_classes)), num_classes, objects)
     weights = torch.tensor(np.ones([num_classes], np.float32)).to(device)
     model_eval = model.eval().to(device)
     hists, loss_sum = [], torch.zeros((), dtype=torch.float64, device=device)
@@ -418,6 +433,4 @@ def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lova
             tot[k] += m[k]
     metrics = {k: tot[k] / n for k in keys}
     metrics["Loss"] = float(loss_sum.item()) / n
-    for a in accs:
-        metrics.update(a.metrics())
-    return metrics
+    return _read_counts(metrics, accs)

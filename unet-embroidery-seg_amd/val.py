@@ -11,6 +11,10 @@ synthetic test split (`--data-path synthetic`, binary / multitask only).
 IoU at `--boundary-iou-d` pixels and HD95 (unetseg_hip/boundary.py), printed after the usual lines.
 `--skeleton-metrics` adds clDice, Skeleton Precision and Skeleton Recall on hard skeletons
 (unetseg_hip/skeleton.py; `--skeleton-max-passes` caps the thinning passes), printed after those.
+`--object-metrics` adds the object-level keys of unetseg_hip/objects.py on connected components of
+`--object-connectivity` (after dropping predicted components below `--object-min-area` pixels): PQ, SQ, Object
+F1 / Precision / Recall, Object F1@[.5:.95], Detection Recall, False Object Rate, Split Rate and Merge Rate,
+printed last.
 
 `--curve-metrics` (binary and multitask) adds the operating-point and calibration keys of
 unetseg_hip/curve.py from a score histogram of `--curve-bins` bins counted on the device: the best-IoU
@@ -40,6 +44,7 @@ from unetseg_hip import losses  # noqa: E402
 from unetseg_hip.boundary import KEYS as BOUNDARY_KEYS, Accumulator as BoundaryAccumulator  # noqa: E402
 from unetseg_hip.boundary import labels_from_logits  # noqa: E402
 from unetseg_hip import curve as curve_mod  # noqa: E402
+from unetseg_hip.objects import KEYS as OBJECT_KEYS, Accumulator as ObjectsAccumulator  # noqa: E402
 from unetseg_hip.skeleton import KEYS as SKELETON_KEYS, Accumulator as SkeletonAccumulator  # noqa: E402
 from unetseg_hip.tta import MODES as TTA_MODES, TTA  # noqa: E402
 from utils.hf_dataloader import DeviceLoader, HFUnetDataset, make_collate  # noqa: E402
@@ -74,6 +79,18 @@ def print_skeleton(m):
     print("\t".join(f"{m[k]:.4f}" for k in SKELETON_KEYS))
 
 
+def object_options(args):
+    """the `objects` argument of the evaluate loops from the flags; None without --object-metrics"""
+    if not args.object_metrics:
+        return None
+    return {"connectivity": args.object_connectivity, "min_area": args.object_min_area}
+
+
+def print_objects(m):
+    print("\t".join(f"{LogColor.RED}{k}{LogColor.RESET}" for k in OBJECT_KEYS))
+    print("\t".join(f"{m[k]:.4f}" for k in OBJECT_KEYS))
+
+
 def curve_accumulator(args):
     """the `curve` argument of the evaluate loops from the flags; None without --curve-metrics"""
     if not args.curve_metrics:
@@ -105,6 +122,7 @@ def val(args):
     boundary = boundary_options(args)
     skeleton = skeleton_options(args)
     cacc = curve_accumulator(args)
+    objects = object_options(args)
     num_classes = args.num_classes + 1 if args.task == "multiclass" else 2  # val.py:22-27
     device = torch.device(args.device)
     input_shape = [args.input_size] * 2
@@ -135,7 +153,7 @@ def val(args):
         m = evaluate_binary(model, loader, device, loss_name=args.loss, pos_weight=None, ignore_index=None,
                             boundary=boundary, boundary_weight=args.boundary_loss_weight,
                             boundary_normalize=not args.boundary_loss_pixels, cldice_weight=args.cldice_weight,
-                            cldice_iters=args.cldice_iters, skeleton=skeleton, curve=cacc)
+                            cldice_iters=args.cldice_iters, skeleton=skeleton, curve=cacc, objects=objects)
         print(f"{LogColor.RED}Dice{LogColor.RESET}\t{LogColor.RED}IoU{LogColor.RESET}\t{LogColor.RED}Precision"
               f"{LogColor.RESET}\t{LogColor.RED}Recall{LogColor.RESET}\t{LogColor.RED}Accuracy{LogColor.RESET}")
         print(f"{m['Dice']:.4f}\t{m['IoU']:.4f}\t{m['Precision']:.4f}\t{m['Recall']:.4f}\t{m['Accuracy']:.4f}")
@@ -145,20 +163,26 @@ def val(args):
             print_skeleton(m)
         if cacc is not None:
             report_curve(args, cacc, m)
+        if objects is not None:
+            print_objects(m)
         return m
     if args.task == "multiclass":
         m = evaluate(model, loader, device, dice_loss=True, focal_loss=False, num_classes=num_classes,
-                     lovasz_softmax=args.loss == "lovasz_softmax", boundary=boundary, skeleton=skeleton)
-        print({k: v for k, v in m.items() if k not in BOUNDARY_KEYS and k not in SKELETON_KEYS})
+                     lovasz_softmax=args.loss == "lovasz_softmax", boundary=boundary, skeleton=skeleton,
+                     objects=objects)
+        print({k: v for k, v in m.items() if k not in BOUNDARY_KEYS + SKELETON_KEYS + OBJECT_KEYS})
         if boundary is not None:
             print_boundary(m)
         if skeleton is not None:
             print_skeleton(m)
+        if objects is not None:
+            print_objects(m)
         return m
 
     model.eval()
     bacc = None if boundary is None else BoundaryAccumulator(boundary)
     sacc = None if skeleton is None else SkeletonAccumulator(skeleton)
+    oacc = None if objects is None else ObjectsAccumulator(objects)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     per_cls = torch.zeros(3, 2, dtype=torch.int64, device=device)  # [class][correct, count]
     with torch.no_grad():
@@ -166,9 +190,9 @@ def val(args):
             images, seg_t, cls_t = images.to(device), seg_t.to(device), cls_t.to(device)
             seg_logits, cls_logits = model(images)
             losses.binary_confusion(seg_logits, seg_t, conf)
-            if bacc is not None or sacc is not None:
+            if bacc is not None or sacc is not None or oacc is not None:
                 seg_pred = labels_from_logits(seg_logits)
-                for acc_ in (bacc, sacc):
+                for acc_ in (bacc, sacc, oacc):
                     if acc_ is not None:
                         acc_.add(seg_pred, seg_t)
             if cacc is not None:
@@ -200,6 +224,9 @@ def val(args):
     if cacc is not None:
         m.update(cacc.metrics())
         report_curve(args, cacc, m)
+    if oacc is not None:
+        m.update(oacc.metrics())
+        print_objects(m)
     return m
 
 
@@ -238,6 +265,15 @@ def parse_args(argv=None):
     p.add_argument("--skeleton-max-passes", default=None, type=int,
                    help="cap of the thinning passes; default min(H, W) // 2 + 8.  An image still losing pixels at the "
                         "cap is an error, not a silently wrong score")
+    p.add_argument("--object-metrics", action="store_true",
+                   help="also report PQ, SQ, Object F1 / Precision / Recall, Object F1@[.5:.95], Detection Recall, "
+                        "False Object Rate, Split Rate and Merge Rate of the connected components (class 1; multiclass: "
+                        "the mean over the classes with a target object)")
+    p.add_argument("--object-connectivity", default=8, type=int, choices=[4, 8],
+                   help="connectivity of the objects of --object-metrics")
+    p.add_argument("--object-min-area", default=0, type=int,
+                   help="with --object-metrics: drop predicted components below this area first, as predict.py "
+                        "--min-area does")
     p.add_argument("--curve-metrics", action="store_true",
                    help="also report the best-IoU threshold with its IoU and F1, IoU at 0.5, AP, AUROC and ECE from a "
                         "score histogram, and write curve.csv and threshold.json (--task binary and multitask)")
@@ -260,6 +296,8 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.skeleton_max_passes is not None and args.skeleton_max_passes < 0:
         p.error("--skeleton-max-passes must be >= 0")
+    if args.object_min_area < 0:
+        p.error("--object-min-area must be >= 0")
     if args.curve_metrics:
         if args.task == "multiclass":
             p.error("--curve-metrics needs --task binary or multitask (one-vs-rest softmax scores are out of scope)")
