@@ -221,10 +221,10 @@ def test_val_flags_round_trip():
 
     a = val.parse_args([])
     assert (a.boundary_metrics, a.boundary_tolerance, a.boundary_iou_d) == (False, 2.0, 0)
-    assert val.boundary_options(a) is None
+    assert val.metric_options(a)["boundary"] is None
     a = val.parse_args(["--boundary-metrics", "--boundary-tolerance", "3.5", "--boundary-iou-d", "7"])
-    assert val.boundary_options(a) == {"tolerance": 3.5, "biou_d": 7}
-    assert val.boundary_options(val.parse_args(["--boundary-metrics"])) == {"tolerance": 2.0, "biou_d": None}
+    assert val.metric_options(a)["boundary"] == {"tolerance": 3.5, "biou_d": 7}
+    assert val.metric_options(val.parse_args(["--boundary-metrics"]))["boundary"] == {"tolerance": 2.0, "biou_d": None}
 
 
 def test_python_layer_refuses_what_is_no_gpu_map():

@@ -400,5 +400,5 @@ def test_val_flags():
 
     a = val.parse_args(["--boundary-metrics"])
     assert a.boundary_metrics and a.boundary_tolerance == 2.0 and a.boundary_iou_d == 0
-    assert val.boundary_options(a) == {"tolerance": 2.0, "biou_d": None}
-    assert val.boundary_options(val.parse_args([])) is None
+    assert val.metric_options(a)["boundary"] == {"tolerance": 2.0, "biou_d": None}
+    assert val.metric_options(val.parse_args([]))["boundary"] is None

@@ -166,8 +166,8 @@ def test_entry_point_flags_default_to_off():
         for bad in (["--object-connectivity", "6"], ["--object-min-area", "-2"]):
             with pytest.raises(SystemExit):
                 mod.parse_args(bad)
-    assert val.object_options(val.parse_args([])) is None
-    assert val.object_options(val.parse_args(["--object-metrics", "--object-min-area", "5"])) == \
+    assert val.metric_options(val.parse_args([]))["objects"] is None
+    assert val.metric_options(val.parse_args(["--object-metrics", "--object-min-area", "5"]))["objects"] == \
         {"connectivity": 8, "min_area": 5}
 
 
@@ -184,8 +184,11 @@ def test_evaluate_loops_take_the_option():
     names = list(inspect.signature(te.evaluate_binary).parameters)
     assert names[names.index("curve") + 1] == "objects" and names[-2:] == ["cldice_weight", "cldice_iters"]
     assert inspect.signature(te.evaluate_binary).parameters["objects"].default is None
-    assert te._metric_accs(None, None) == [] and te._metric_accs(None, None, objects=None) == []
-    accs = te._metric_accs(None, {}, (1, 2), 3, {"connectivity": 4})
+    from unetseg_hip.metricset import MetricSet
+
+    assert te.MetricSet is MetricSet  # what the three loops build
+    assert MetricSet(None, None).accs == [] and MetricSet(None, None, objects=None).accs == []
+    accs = MetricSet(None, {}, None, {"connectivity": 4}, (1, 2), 3).accs
     assert [type(a).__module__ for a in accs] == ["unetseg_hip.skeleton", "unetseg_hip.objects"]
     assert accs[1].classes == (1, 2) and accs[1].ignore_index == 3 and accs[1].connectivity == 4
 

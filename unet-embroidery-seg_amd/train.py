@@ -39,8 +39,9 @@ from model.model_factory import SUPPORTED_MODELS, build_model, load_weights_flex
 from model.unet_multitask import MultiTaskLoss  # noqa: E402
 from model.unet_training import get_lr_scheduler, lovasz_hinge_loss, set_optimizer_lr, weights_init  # noqa: E402
 from unetseg_hip.arena import FusedAdam  # noqa: E402
-from unetseg_hip.curve import Accumulator as CurveAccumulator, write_threshold  # noqa: E402
+from unetseg_hip.curve import write_threshold  # noqa: E402
 from unetseg_hip.ddp import GradBuckets, init_from_env, local_device  # noqa: E402
+from utils import metric_args  # noqa: E402
 from utils.hf_dataloader import DeviceLoader, HFUnetDataset, make_collate  # noqa: E402
 from utils.vis_export import export_binary_visuals  # noqa: E402
 from utils.synthetic import SyntheticSegDataset, collate  # noqa: E402
@@ -189,12 +190,12 @@ def train(args):
     best_path, last_path = os.path.join(weights_folder, "best.pth"), os.path.join(weights_folder, "last.pth")
     last_raw_path = os.path.join(weights_folder, "last_raw.pth")  # --ema-decay: the live (not averaged) weights
     averaged = optimizer.averaged if args.ema_decay > 0 else contextlib.nullcontext
-    # the clDice metric of the validation and test passes (model selection stays on IoU / Mean IoU)
-    skel = {"max_passes": args.skeleton_max_passes} if args.skeleton_metrics else None
-    # the operating-point and calibration keys of the binary head (unetseg_hip/curve.py), the same way
-    crv = {"bins": args.curve_bins} if args.curve_metrics else None
-    # the object-level keys (unetseg_hip/objects.py: PQ, object F1, split and merge rates), the same way
-    obj = {"connectivity": args.object_connectivity, "min_area": args.object_min_area} if args.object_metrics else None
+    # the optional metrics of the validation and test passes: clDice, the operating-point and calibration keys of the
+    # binary head, the object-level keys (model selection stays on IoU / Mean IoU)
+    extra = metric_args.metric_options(args)
+    crv = extra["curve"]
+    if args.task == "multiclass":
+        del extra["curve"]  # `evaluate` has no binary head to take it
     train_losses, val_losses, history = [], [], []
     t0 = time.time()
     for epoch in range(args.epochs):
@@ -226,19 +227,17 @@ def train(args):
         # before the next epoch trains (BatchNorm statistics are the live ones either way)
         with averaged():
             if args.task == "multitask":
-                metrics = evaluate_multitask(model, val_loader, device, criterion, mvb, skeleton=skel, curve=crv,
-                                             objects=obj)
+                metrics = evaluate_multitask(model, val_loader, device, criterion, mvb, **extra)
                 print(f"Val - IoU: {metrics['IoU']:.4f}, Dice: {metrics['Dice']:.4f}, "
                       f"Cls Acc: {metrics['Cls Acc']:.2f}%")
                 score = float(metrics["IoU"])
             elif args.task == "binary":
                 metrics = evaluate_binary(model, val_loader, device, loss_name=args.loss, pos_weight=pos_weight,
-                                          ignore_index=None, max_batches=mvb, skeleton=skel, curve=crv, objects=obj,
-                                          **bnd)
+                                          ignore_index=None, max_batches=mvb, **extra, **bnd)
                 score = float(metrics["IoU"])
             else:
                 metrics = evaluate(model, val_loader, device, args.use_dice, args.loss == "focal", num_classes,
-                                   lovasz_softmax=args.loss == "lovasz_softmax", skeleton=skel, objects=obj)
+                                   lovasz_softmax=args.loss == "lovasz_softmax", **extra)
                 score = float(metrics["Mean IoU"])
             val_losses.append(metrics["Loss"])
             history.append(metrics)
@@ -268,15 +267,12 @@ def train(args):
             if test_loader is None:
                 pass
             elif args.task == "multitask":
-                test_metrics = evaluate_multitask(model, test_loader, device, criterion, mtest, skeleton=skel,
-                                                  curve=crv, objects=obj)
+                test_metrics = evaluate_multitask(model, test_loader, device, criterion, mtest, **extra)
             elif args.task == "multiclass":
-                test_metrics = evaluate(model, test_loader, device, True, False, num_classes, skeleton=skel,
-                                        objects=obj)
+                test_metrics = evaluate(model, test_loader, device, True, False, num_classes, **extra)
             else:
                 test_metrics = evaluate_binary(model, test_loader, device, loss_name=args.loss, pos_weight=pos_weight,
-                                               ignore_index=None, max_batches=mtest, skeleton=skel, curve=crv,
-                                               objects=obj, **bnd)
+                                               ignore_index=None, max_batches=mtest, **extra, **bnd)
             with open(os.path.join(exp_folder, "test_metrics.json"), "w", encoding="utf-8") as f:
                 json.dump(test_metrics, f, ensure_ascii=False, indent=2)
             # fixed-sample visual export of the test split (train.py:476-486; HF datasets only)
@@ -325,26 +321,7 @@ def parse_args(argv=None):
                    help="adds this multiple of the soft-clDice (centerline Dice) loss to the region loss (--task binary "
                         "and multitask; constant over the run)")
     p.add_argument("--cldice-iters", default=3, type=int, help="levels of the soft skeleton (0 .. 64)")
-    p.add_argument("--skeleton-metrics", action="store_true",
-                   help="validation and test also report clDice, Skeleton Precision and Skeleton Recall on hard "
-                        "skeletons (into the metric history); model selection stays on IoU / Mean IoU")
-    p.add_argument("--skeleton-max-passes", default=None, type=int,
-                   help="cap of the thinning passes; default min(H, W) // 2 + 8")
-    p.add_argument("--curve-metrics", action="store_true",
-                   help="validation and test also report the best-IoU threshold with its IoU and F1, IoU at 0.5, AP, "
-                        "AUROC and ECE of the binary head (into the metric history; --task binary and multitask); "
-                        "threshold.json holds the best epoch's validation threshold; model selection stays on IoU")
-    p.add_argument("--curve-bins", default=1000, type=int,
-                   help="bins K of the score histogram (even, a multiple of 10, at most 4096)")
-    p.add_argument("--object-metrics", action="store_true",
-                   help="validation and test also report PQ, SQ, Object F1 / Precision / Recall, Object F1@[.5:.95], "
-                        "Detection Recall, False Object Rate, Split Rate and Merge Rate of the connected components "
-                        "(into the metric history); model selection stays on IoU / Mean IoU")
-    p.add_argument("--object-connectivity", default=8, type=int, choices=[4, 8],
-                   help="connectivity of the objects of --object-metrics")
-    p.add_argument("--object-min-area", default=0, type=int,
-                   help="with --object-metrics: drop predicted components below this area first, as predict.py "
-                        "--min-area does")
+    metric_args.add_metric_args(p)  # validation and test report them into the metric history
     p.add_argument("--pos-weight", default="auto")
     p.add_argument("--pos-weight-samples", default=80, type=int)
     p.add_argument("--use-dice", action=argparse.BooleanOptionalAction, default=True)
@@ -380,17 +357,7 @@ def parse_args(argv=None):
     check_loss_term_args(p, args)
     if not 0.0 <= args.ema_decay < 1.0:
         p.error("--ema-decay must be in [0, 1)")
-    if args.skeleton_max_passes is not None and args.skeleton_max_passes < 0:
-        p.error("--skeleton-max-passes must be >= 0")
-    if args.object_min_area < 0:
-        p.error("--object-min-area must be >= 0")
-    if args.curve_metrics:
-        if args.task == "multiclass":
-            p.error("--curve-metrics needs --task binary or multitask (one-vs-rest softmax scores are out of scope)")
-        try:
-            CurveAccumulator({"bins": args.curve_bins})
-        except ValueError as e:
-            p.error(f"--curve-bins: {e}")
+    metric_args.check_metric_args(p, args)
     if args.pos_weight == "":
         args.pos_weight = None
     return args

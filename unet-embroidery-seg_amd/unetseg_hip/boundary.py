@@ -16,6 +16,8 @@ import math
 
 import torch
 
+from .classmap import ClassCounts, _ignore, _map, _out_counts, _stream
+from .classmap import labels_from_logits  # noqa: F401  (the name callers and INTEGRATION.md use)
 from .lib import lib
 
 #: ``sqdist`` of an image without a site (UNETSEG_EDT_INF)
@@ -24,66 +26,6 @@ INF = 1 << 30
 MAX_K = 65536
 
 KEYS = ("Boundary Precision", "Boundary Recall", "Boundary F1", "Boundary IoU", "HD95")
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _map(t, what="cls", dtypes=(torch.int32,)):
-    """the map as a contiguous [N,H,W] view"""
-    if not torch.is_tensor(t) or t.dtype not in dtypes or not t.is_cuda or t.dim() not in (2, 3):
-        names = " or ".join(str(d).replace("torch.", "") for d in dtypes)
-        raise ValueError(f"{what} must be a {names} [H,W] or [N,H,W] tensor on the GPU, got "
-                         f"{t.dtype if torch.is_tensor(t) else type(t)} "
-                         f"{tuple(t.shape) if torch.is_tensor(t) else ''}")
-    t = t.contiguous()
-    return t.unsqueeze(0) if t.dim() == 2 else t
-
-
-def _ignore(ignore_index):
-    if ignore_index is None:
-        return -1
-    if int(ignore_index) == -1:
-        raise ValueError("ignore_index -1 stands for None in the kernels; use another value")
-    return int(ignore_index)
-
-
-def _out_counts(out, n, device):
-    """the array a ``counts`` adds to: ``out`` checked, or zeros when it is None"""
-    if out is None:
-        return torch.zeros(n, dtype=torch.int64, device=device)
-    if (not torch.is_tensor(out) or out.dtype != torch.int64 or out.device != device or out.dim() != 1
-            or out.numel() != n or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous int64 [{n}] tensor on {device}")
-    return out
-
-
-def _int_target(target, ignore_index):
-    """an evaluation loop's target [B,H,W] or [B,1,H,W] as int32 [B,H,W]; a float target is read as
-    ``losses.binary_confusion`` reads it: class 1 where it equals 1, ``ignore_index`` kept"""
-    tgt = target.detach()
-    if tgt.is_floating_point():
-        lab = (tgt == 1).to(torch.int32)
-        if ignore_index is not None:
-            lab = torch.where(tgt == ignore_index, torch.full_like(lab, int(ignore_index)), lab)
-        tgt = lab
-    if tgt.dim() == 4 and tgt.shape[1] == 1:
-        tgt = tgt[:, 0]
-    return tgt.to(torch.int32)
-
-
-def _class_mean(rows, several, has_target, read, keys):
-    """an accumulator's metrics from its per-class count rows: ``read(row)`` of the one class, or with
-    ``several`` classes the mean per key over the rows that ``has_target``; 0.0 when none is left"""
-    if several:
-        rows = [r for r in rows if has_target(r)]
-    per = [read(r) for r in rows]
-    if not per:
-        return dict.fromkeys(keys, 0.0)
-    if len(per) == 1:
-        return per[0]
-    return {k: sum(m[k] for m in per) / len(per) for k in keys}
 
 
 def chunk():
@@ -153,23 +95,6 @@ def counts(pred, target, c=1, K=4096, biou_d=None, ignore_index=None, out=None):
     return out
 
 
-def labels_from_logits(outputs):
-    """int32 [B,H,W] class map of logits [B,C,H,W]: C >= 2 the argmax with a tie going to the lower class,
-    C == 1 ``logit > 0``: the rule of ``losses.binary_confusion`` (argmax with the tie to class 0, and
-    sigmoid > 0.5, which a zero logit does not pass)"""
-    if not torch.is_tensor(outputs) or outputs.dim() != 4:
-        raise ValueError("outputs must be logits [B,C,H,W]")
-    out = outputs.detach().float()
-    if out.shape[1] == 1:
-        return (out[:, 0] > 0).to(torch.int32)
-    best, lab = out[:, 0], torch.zeros(out[:, 0].shape, dtype=torch.int32, device=out.device)
-    for k in range(1, out.shape[1]):  # strictly greater: a tie keeps the lower class
-        take = out[:, k] > best
-        best = torch.where(take, out[:, k], best)
-        lab = torch.where(take, torch.full_like(lab, k), lab)
-    return lab
-
-
 def metrics_from_counts(counts, K, tolerance=2.0):
     """host, float64: the five ``KEYS`` from a ``counts`` array (tensor, array or list) taken with this K.
 
@@ -211,38 +136,33 @@ def metrics_from_counts(counts, K, tolerance=2.0):
             "HD95": hd95}
 
 
-class Accumulator:
-    """the boundary counts of an evaluation loop: one device array per class, added to per batch, read once.
+class Accumulator(ClassCounts):
+    """the boundary counts of an evaluation loop (``ClassCounts``).
 
     ``options`` is the entry points' ``boundary`` dict: ``{"tolerance": px (default 2.0), "biou_d": px or
-    None / 0 (2 % of the diagonal), "K": squared distance (default 4096)}``."""
+    None / 0 (2 % of the diagonal), "K": squared distance (default 4096)}``.  A class counts in the mean when it
+    has a target edge pixel in the split."""
+
+    FAMILY, OPTIONS, KEYS = "boundary", ("tolerance", "biou_d", "K"), KEYS
 
     def __init__(self, options, classes=(1,), ignore_index=None):
-        unknown = set(options) - {"tolerance", "biou_d", "K"}
-        if unknown:
-            raise ValueError(f"unknown boundary options {sorted(unknown)}")
+        super().__init__(options, classes, ignore_index)
         self.tolerance = float(options.get("tolerance", 2.0))
         self.biou_d = options.get("biou_d") or None
         self.K = int(options.get("K", 4096))
         if self.tolerance < 0 or self.tolerance ** 2 > self.K:
             raise ValueError(f"tolerance^2 = {self.tolerance ** 2} must lie in 0 .. K = {self.K}")
-        self.classes = tuple(classes)
-        self.ignore_index = ignore_index
-        self.out = None
 
-    def add(self, pred, target):
-        """pred int32 [B,H,W] (``labels_from_logits``); target [B,H,W] or [B,1,H,W] on the same device, integer,
-        or float read as ``losses.binary_confusion`` reads it: class 1 where it equals 1, ``ignore_index`` kept"""
-        tgt = _int_target(target, self.ignore_index)
-        if self.out is None:
-            self.out = torch.zeros(len(self.classes), 2 * (self.K + 2) + 2, dtype=torch.int64, device=pred.device)
+    @property
+    def N(self):
+        return 2 * (self.K + 2) + 2
+
+    def count(self, pred, tgt):
         for c, out in zip(self.classes, self.out):
             counts(pred, tgt, c, self.K, self.biou_d, self.ignore_index, out)
 
-    def metrics(self):
-        """the five keys after one host read; with several classes the mean over those with a target edge
-        pixel in the split, 0.0 without one"""
-        n = 2 * (self.K + 2) + 2
-        rows = self.out.tolist() if self.out is not None else [[0] * n for _ in self.classes]
-        return _class_mean(rows, len(self.classes) > 1, lambda c: sum(c[self.K + 2:2 * self.K + 4]) > 0,
-                           lambda c: metrics_from_counts(c, self.K, self.tolerance), KEYS)
+    def has_target(self, row):
+        return sum(row[self.K + 2:2 * self.K + 4]) > 0
+
+    def read(self, row):
+        return metrics_from_counts(row, self.K, self.tolerance)

@@ -16,21 +16,8 @@ import ctypes
 
 import torch
 
+from .classmap import _map, _stream
 from .lib import lib
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _map(t, what="cls"):
-    """the map as a contiguous [N,H,W] view"""
-    if not torch.is_tensor(t) or t.dtype != torch.int32 or not t.is_cuda or t.dim() not in (2, 3):
-        raise ValueError(f"{what} must be an int32 [H,W] or [N,H,W] tensor on the GPU, got "
-                         f"{t.dtype if torch.is_tensor(t) else type(t)} "
-                         f"{tuple(t.shape) if torch.is_tensor(t) else ''}")
-    t = t.contiguous()
-    return t.unsqueeze(0) if t.dim() == 2 else t
 
 
 def tile():

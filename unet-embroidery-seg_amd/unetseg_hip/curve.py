@@ -2,7 +2,7 @@
 (csrc/curve.hip).
 
 Every binary decision of the project is taken at probability 0.5 (``losses.binary_confusion``,
-``boundary.labels_from_logits``).  ``hist`` bins the logit ``z`` (``o0`` of a one-channel head, ``o1 - o0`` of a
+``classmap.labels_from_logits``).  ``hist`` bins the logit ``z`` (``o0`` of a one-channel head, ``o1 - o0`` of a
 two-channel one) of every valid pixel against a fixed table of K - 1 logit thresholds, ``edges``, separately for
 positive (target == 1) and negative pixels.  Threshold k stands for probability k / K: its edge is
 ``theta_k = logit(k / K)``, the prediction at it is ``z > theta_k``, which is ``bin >= k``, and k = K / 2 is the
@@ -18,7 +18,7 @@ import math
 
 import torch
 
-from .boundary import _ignore, _out_counts, _stream
+from .classmap import _ignore, _out_counts, _stream
 from .lib import lib
 from .losses import _prep
 
@@ -90,7 +90,7 @@ def hist(outputs, targets, K=1000, ignore_index=None, out=None):
 def labels_at(outputs, threshold, K=1000):
     """int32 [B,H,W] class map of logits [B,1,H,W] or [B,2,H,W] at ``threshold`` = k / K (an integer
     1 <= k <= K - 1, else ValueError): ``z > theta_k``, the rule ``table`` counts at row k, in torch ops on the
-    tensor's device.  At threshold 0.5 it equals ``boundary.labels_from_logits``."""
+    tensor's device.  At threshold 0.5 it equals ``classmap.labels_from_logits``."""
     K = _check_bins(K)
     k = _threshold_k(threshold, K)
     if not torch.is_tensor(outputs) or outputs.dim() != 4 or outputs.shape[1] not in (1, 2):
@@ -214,6 +214,11 @@ class Accumulator:
         self.ignore_index = ignore_index
         self.out = None
         self._host = None
+
+    @property
+    def keys(self):
+        """the keys ``metrics`` returns, in its order"""
+        return KEYS + (KEYS_AT if self.threshold is not None else ())
 
     def add(self, logits, targets):
         """logits [B,1,H,W] or [B,2,H,W] and targets as ``hist`` takes them"""

@@ -19,9 +19,8 @@ import ctypes
 import torch
 
 from . import ccl
-from .boundary import _class_mean, _int_target, _out_counts, _stream
+from .classmap import ClassCounts, _check_class, _out_counts, _pair, _stream
 from .lib import lib
-from .skeleton import _check_class, _pair
 
 KEYS = ("PQ", "SQ", "Object F1", "Object Precision", "Object Recall", "Object F1@[.5:.95]", "Detection Recall",
         "False Object Rate", "Split Rate", "Merge Rate")
@@ -165,31 +164,25 @@ def metrics_from_counts(counts):
             "Split Rate": _ratio(c[4], n_gt), "Merge Rate": _ratio(c[5], n_pred)}
 
 
-class Accumulator:
-    """the object counts of an evaluation loop: one device row per class, added to per batch, read once.
+class Accumulator(ClassCounts):
+    """the object counts of an evaluation loop (``ClassCounts``).
 
     ``options`` is the entry points' ``objects`` dict: ``{"connectivity": 4 or 8 (default 8), "min_area": int
     (default 0)}``.  ``min_area`` > 1 passes the prediction through ``ccl.clean(pred, min_area, 0, connectivity)``
     first, the cleanup of ``predict.py --min-area``, so the numbers are those of the map that would be shipped.  The
-    two labellings and stats of a batch are done once and shared by the classes."""
+    two labellings and stats of a batch are done once and shared by the classes.  A class counts in the mean when
+    it has a target object in the split."""
+
+    FAMILY, OPTIONS, N, KEYS = "objects", ("connectivity", "min_area"), N_COUNTS, KEYS
 
     def __init__(self, options, classes=(1,), ignore_index=None):
-        unknown = set(options) - {"connectivity", "min_area"}
-        if unknown:
-            raise ValueError(f"unknown objects options {sorted(unknown)}")
+        super().__init__(options, [_check_class(c, ignore_index) for c in classes], ignore_index)
         self.connectivity = _connectivity(options.get("connectivity", 8))
         self.min_area = int(options.get("min_area", 0) or 0)
         if self.min_area < 0:
             raise ValueError(f"min_area must not be negative, got {self.min_area}")
-        self.classes = tuple(_check_class(c, ignore_index) for c in classes)
-        self.ignore_index = ignore_index
-        self.out = None
 
-    def add(self, pred, target):
-        """pred int32 [B,H,W] (``boundary.labels_from_logits``); target as ``boundary.Accumulator.add`` takes it"""
-        tgt = _int_target(target, self.ignore_index)
-        if self.out is None:
-            self.out = torch.zeros(len(self.classes), N_COUNTS, dtype=torch.int64, device=pred.device)
+    def count(self, pred, tgt):
         if self.min_area > 1:
             pred = ccl.clean(pred, self.min_area, 0, self.connectivity)
         _, _, pm, tm = _pair(pred, tgt, self.ignore_index)
@@ -200,11 +193,11 @@ class Accumulator:
             lab.pairs(c)
             lab.match(c, out)
 
-    def metrics(self):
-        """the ten keys after one host read; with several classes the mean over those that have a target object in
-        the split, 0.0 without one"""
-        rows = self.out.tolist() if self.out is not None else [[0] * N_COUNTS for _ in self.classes]
-        for r in rows:  # a dropped insertion is a bug whatever the class
-            if r[18] > 0:
-                metrics_from_counts(r)
-        return _class_mean(rows, len(self.classes) > 1, lambda r: r[0] > 0, metrics_from_counts, KEYS)
+    def guard(self, row):  # a dropped insertion is a bug whatever the class
+        if row[18] > 0:
+            metrics_from_counts(row)
+
+    def has_target(self, row):
+        return row[0] > 0
+
+    read = staticmethod(metrics_from_counts)

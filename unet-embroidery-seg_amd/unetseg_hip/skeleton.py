@@ -16,12 +16,11 @@ import ctypes
 
 import torch
 
-from .boundary import _class_mean, _ignore, _int_target, _map, _out_counts, _stream
+from .classmap import MAX_CLASS  # noqa: F401  (the largest class value ``thin`` keeps)
+from .classmap import ClassCounts, _check_class, _ignore, _map, _out_counts, _pair, _stream
 from .lib import lib
 
 KEYS = ("clDice", "Skeleton Precision", "Skeleton Recall")
-#: the largest class value ``thin`` keeps
-MAX_CLASS = 255
 
 
 def tile():
@@ -66,27 +65,6 @@ def thin(cls, max_passes=None, return_unconverged=False):
                   ws.data_ptr(), size, _stream(m))
     out = out.view(cls.shape)
     return (out, unc) if return_unconverged else out
-
-
-def _check_class(c, ignore_index):
-    c = int(c)
-    if not 1 <= c <= MAX_CLASS:
-        raise ValueError(f"class must lie in 1 .. {MAX_CLASS}, got {c}")
-    if ignore_index is not None and int(ignore_index) == c:
-        raise ValueError(f"ignore_index is the counted class {c}")
-    return c
-
-
-def _pair(pred, target, ignore_index):
-    """pred and target as [N,H,W], with the pixels whose target is ``ignore_index`` set to 0 in both"""
-    p, t = _map(pred, "pred"), _map(target, "target")
-    if p.shape != t.shape or p.device != t.device:
-        raise ValueError(f"pred {tuple(p.shape)} on {p.device} and target {tuple(t.shape)} on {t.device} differ")
-    if ignore_index is None:
-        return p, t, p, t
-    valid = t != int(ignore_index)
-    zero = torch.zeros_like(t)
-    return p, t, torch.where(valid, p, zero), torch.where(valid, t, zero)
 
 
 def _thin_pair(pm, tm, max_passes):
@@ -144,38 +122,32 @@ def metrics_from_counts(counts):
     return {"clDice": cl, "Skeleton Precision": tprec, "Skeleton Recall": tsens}
 
 
-class Accumulator:
-    """the skeleton counts of an evaluation loop: one device row per class, added to per batch, read once.
+class Accumulator(ClassCounts):
+    """the skeleton counts of an evaluation loop (``ClassCounts``).
 
     ``options`` is the entry points' ``skeleton`` dict: ``{"max_passes": int or None}`` (None:
-    ``default_max_passes``).  The two thinnings of a batch are done once and shared by the classes."""
+    ``default_max_passes``).  The two thinnings of a batch are done once and shared by the classes.  A class counts
+    in the mean when its target skeleton is non-empty in the split."""
+
+    FAMILY, OPTIONS, N, KEYS = "skeleton", ("max_passes",), 6, KEYS
 
     def __init__(self, options, classes=(1,), ignore_index=None):
-        unknown = set(options) - {"max_passes"}
-        if unknown:
-            raise ValueError(f"unknown skeleton options {sorted(unknown)}")
+        super().__init__(options, [_check_class(c, ignore_index) for c in classes], ignore_index)
         self.max_passes = options.get("max_passes")
         if self.max_passes is not None and int(self.max_passes) < 0:
             raise ValueError(f"max_passes must not be negative, got {self.max_passes}")
-        self.classes = tuple(_check_class(c, ignore_index) for c in classes)
-        self.ignore_index = ignore_index
-        self.out = None
 
-    def add(self, pred, target):
-        """pred int32 [B,H,W] (``boundary.labels_from_logits``); target as ``boundary.Accumulator.add`` takes it"""
-        tgt = _int_target(target, self.ignore_index)
-        if self.out is None:
-            self.out = torch.zeros(len(self.classes), 6, dtype=torch.int64, device=pred.device)
+    def count(self, pred, tgt):
         p, t, pm, tm = _pair(pred, tgt, self.ignore_index)
         thinned = _thin_pair(pm, tm, self.max_passes)
         for c, out in zip(self.classes, self.out):
             _counts(pm, t, thinned, c, _ignore(self.ignore_index), out)
 
-    def metrics(self):
-        """the three keys after one host read; with several classes the mean over those whose target skeleton
-        is non-empty in the split, 0.0 without one"""
-        rows = self.out.tolist() if self.out is not None else [[0] * 6 for _ in self.classes]
-        for r in rows:  # an unconverged image spoils every class's counts
-            if r[4] > 0:
-                metrics_from_counts(r)
-        return _class_mean(rows, len(self.classes) > 1, lambda r: r[3] > 0, metrics_from_counts, KEYS)
+    def guard(self, row):  # an unconverged image spoils every class's counts
+        if row[4] > 0:
+            metrics_from_counts(row)
+
+    def has_target(self, row):
+        return row[3] > 0
+
+    read = staticmethod(metrics_from_counts)

@@ -16,10 +16,7 @@ import torch
 from torch.amp import autocast
 
 from unetseg_hip import losses
-from unetseg_hip.boundary import Accumulator as BoundaryAccumulator, labels_from_logits
-from unetseg_hip.curve import Accumulator as CurveAccumulator
-from unetseg_hip.objects import Accumulator as ObjectsAccumulator
-from unetseg_hip.skeleton import Accumulator as SkeletonAccumulator
+from unetseg_hip.metricset import MetricSet
 from utils.utils import get_lr
 
 
@@ -165,49 +162,6 @@ def train_one_epoch_binary(model, optimizer, train_loader, device, loss_name: st
     return float(epoch_loss.item()) / max(seen_batches, 1)
 
 
-def _metric_accs(boundary, skeleton, classes=(1,), ignore_index=None, objects=None):
-    """the count accumulators of an evaluation loop, in the order their keys enter the metrics: the boundary
-    counts with the `boundary` options, the skeleton counts (clDice metric) with the `skeleton` options, the
-    object counts with the `objects` options"""
-    accs = []
-    if boundary is not None:
-        accs.append(BoundaryAccumulator(boundary, classes, ignore_index))
-    if skeleton is not None:
-        accs.append(SkeletonAccumulator(skeleton, classes, ignore_index))
-    if objects is not None:
-        accs.append(ObjectsAccumulator(objects, classes, ignore_index))
-    return accs
-
-
-def _add_counts(accs, logits, targets):
-    """one class map of the logits for the accumulators that are on"""
-    if accs:
-        pred = labels_from_logits(logits)
-        for a in accs:
-            a.add(pred, targets)
-
-
-def _read_counts(metrics, accs, cacc=None):
-    """the accumulators' keys after the loop's own: boundary and skeleton, then the curve's, the objects' last"""
-    late = [a for a in accs if isinstance(a, ObjectsAccumulator)]
-    for a in accs:
-        if a not in late:
-            metrics.update(a.metrics())
-    if cacc is not None:
-        metrics.update(cacc.metrics())
-    for a in late:
-        metrics.update(a.metrics())
-    return metrics
-
-
-def _curve_acc(curve, ignore_index=None):
-    """the score-histogram accumulator of an evaluation loop, or None; a CurveAccumulator is taken as it is, so
-    the caller can read its table after the loop"""
-    if curve is None or isinstance(curve, CurveAccumulator):
-        return curve
-    return CurveAccumulator(curve, ignore_index)
-
-
 def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignore_index=None, max_batches=None,
                     boundary=None, skeleton=None, curve=None, objects=None, boundary_weight=0.0,
                     boundary_normalize=True, cldice_weight=0.0, cldice_iters=3):
@@ -225,8 +179,7 @@ def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignor
     (unetseg_hip/objects.py: PQ, SQ, Object F1 / Precision / Recall, Object F1@[.5:.95], Detection Recall, False
     Object Rate, Split Rate, Merge Rate) from connected components labelled and paired on the device."""
     model_eval = model.eval().to(device)
-    accs = _metric_accs(boundary, skeleton, (1,), ignore_index, objects)
-    cacc = _curve_acc(curve, ignore_index)
+    ms = MetricSet(boundary, skeleton, curve, objects, ignore_index=ignore_index)
     total_loss = torch.zeros((), dtype=torch.float64, device=device)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     seen_batches = 0
@@ -238,16 +191,15 @@ def evaluate_binary(model, val_loader, device, loss_name: str, pos_weight, ignor
                                             boundary_normalize, cldice_weight, cldice_iters)
             total_loss += loss
             losses.binary_confusion(outputs, pngs, conf, ignore_index)
-            _add_counts(accs, outputs, pngs)
-            if cacc is not None:
-                cacc.add(outputs, pngs)
+            ms.add(outputs, pngs)
             seen_batches += 1
             if max_batches is not None and seen_batches >= max_batches:
                 break
     tp, fp, fn, tn = (float(v) for v in conf.tolist())
     metrics = binary_segmentation_metrics(tp, fp, fn, tn)
     metrics["Loss"] = float(total_loss.item() / max(seen_batches, 1))
-    return _read_counts(metrics, accs, cacc)
+    metrics.update(ms.metrics())
+    return metrics
 
 
 def train_one_epoch_multitask(model, optimizer, train_loader, device, criterion, scaler, amp=True, max_batches=None,
@@ -293,8 +245,7 @@ def evaluate_multitask(model, loader, device, criterion, max_batches=None, bound
     with P = sigmoid(seg) > 0.5 (fused confusion kernel, u64 counts on the device); cls accuracy %.
     boundary, skeleton, curve, objects: as in evaluate_binary, on the segmentation head."""
     model.eval()
-    accs = _metric_accs(boundary, skeleton, objects=objects)
-    cacc = _curve_acc(curve)
+    ms = MetricSet(boundary, skeleton, curve, objects)
     sums = torch.zeros(3, dtype=torch.float64, device=device)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     correct = torch.zeros((), dtype=torch.int64, device=device)
@@ -309,9 +260,7 @@ def evaluate_multitask(model, loader, device, criterion, max_batches=None, bound
             loss, seg_loss, cls_loss = criterion(seg_logits, cls_logits, seg_targets, cls_targets)
             sums += torch.stack([loss, seg_loss, cls_loss]).double()
             losses.binary_confusion(seg_logits, seg_targets, conf)
-            _add_counts(accs, seg_logits, seg_targets)
-            if cacc is not None:
-                cacc.add(seg_logits, seg_targets)
+            ms.add(seg_logits, seg_targets)
             correct += cls_logits.argmax(1).eq(cls_targets).sum()
             total += cls_targets.size(0)
     tp, fp, fn, _tn = (float(v) for v in conf.tolist())
@@ -321,7 +270,8 @@ def evaluate_multitask(model, loader, device, criterion, max_batches=None, bound
     metrics = {"Loss": l, "Seg Loss": sl, "Cls Loss": cl, "IoU": tp / (tp + fp + fn + 1e-6),
                "Dice": 2 * tp / ((tp + fp) + (tp + fn) + 1e-6),
                "Cls Acc": 100.0 * float(correct.item()) / max(total, 1)}
-    return _read_counts(metrics, accs, cacc)
+    metrics.update(ms.metrics())
+    return metrics
 
 
 # ------------------------------------------------------------------------------------------------
@@ -412,7 +362,7 @@ def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lova
     objects: None, or {"connectivity": 4 or 8, "min_area": int} to add the object-level keys in the same way: the
     mean over the classes that have a target object in the split."""
     import numpy as np
-    accs = _metric_accs(boundary, skeleton, tuple(range(1, num_classes)), num_classes, objects)
+    ms = MetricSet(boundary, skeleton, None, objects, range(1, num_classes), num_classes)
     weights = torch.tensor(np.ones([num_classes], np.float32)).to(device)
     model_eval = model.eval().to(device)
     hists, loss_sum = [], torch.zeros((), dtype=torch.float64, device=device)
@@ -423,7 +373,7 @@ def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lova
             loss_sum += _mc_loss(outputs, pngs, labels, weights, num_classes, dice_loss, focal_loss,
                                  lovasz_softmax).double()
             hists.append(losses.mc_confusion(outputs, pngs))
-            _add_counts(accs, outputs, pngs)
+            ms.add(outputs, pngs)
     n = max(len(val_loader), 1)
     keys = ("Pixel Accuracy", "Mean Accuracy", "Mean IoU", "Frequency Weighted IoU")
     tot = dict.fromkeys(keys, 0.0)
@@ -433,4 +383,5 @@ def evaluate(model, val_loader, device, dice_loss, focal_loss, num_classes, lova
             tot[k] += m[k]
     metrics = {k: tot[k] / n for k in keys}
     metrics["Loss"] = float(loss_sum.item()) / n
-    return _read_counts(metrics, accs)
+    metrics.update(ms.metrics())
+    return metrics

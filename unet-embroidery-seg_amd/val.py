@@ -41,12 +41,10 @@ from torch.utils.data import DataLoader  # noqa: E402
 
 from model.model_factory import SUPPORTED_MODELS, build_model  # noqa: E402
 from unetseg_hip import losses  # noqa: E402
-from unetseg_hip.boundary import KEYS as BOUNDARY_KEYS, Accumulator as BoundaryAccumulator  # noqa: E402
-from unetseg_hip.boundary import labels_from_logits  # noqa: E402
 from unetseg_hip import curve as curve_mod  # noqa: E402
-from unetseg_hip.objects import KEYS as OBJECT_KEYS, Accumulator as ObjectsAccumulator  # noqa: E402
-from unetseg_hip.skeleton import KEYS as SKELETON_KEYS, Accumulator as SkeletonAccumulator  # noqa: E402
+from unetseg_hip.metricset import MetricSet  # noqa: E402
 from unetseg_hip.tta import MODES as TTA_MODES, TTA  # noqa: E402
+from utils import metric_args  # noqa: E402
 from utils.hf_dataloader import DeviceLoader, HFUnetDataset, make_collate  # noqa: E402
 from utils.synthetic import SyntheticSegDataset, collate  # noqa: E402
 from utils.train_and_eval import LogColor, evaluate, evaluate_binary  # noqa: E402
@@ -55,47 +53,20 @@ from utils.utils import check_loss_term_args  # noqa: E402
 CLASS_NAMES = ["动物类", "植物类", "复合类"]  # val.py:84
 
 
-def boundary_options(args):
-    """the `boundary` argument of the evaluate loops from the flags; None without --boundary-metrics"""
-    if not args.boundary_metrics:
-        return None
-    return {"tolerance": args.boundary_tolerance, "biou_d": args.boundary_iou_d or None}
+def metric_options(args):
+    """the `boundary`, `skeleton`, `curve` and `objects` arguments of the evaluate loops from the flags: the shared
+    ones, and this entry point's --boundary-* and --threshold; None for a family whose flag is off"""
+    opts = metric_args.metric_options(args)
+    if args.boundary_metrics:
+        opts["boundary"] = {"tolerance": args.boundary_tolerance, "biou_d": args.boundary_iou_d or None}
+    if opts["curve"] is not None:
+        opts["curve"]["threshold"] = args.threshold
+    return opts
 
 
-def print_boundary(m):
-    print("\t".join(f"{LogColor.RED}{k}{LogColor.RESET}" for k in BOUNDARY_KEYS))
-    print("\t".join(f"{m[k]:.4f}" for k in BOUNDARY_KEYS))
-
-
-def skeleton_options(args):
-    """the `skeleton` argument of the evaluate loops from the flags; None without --skeleton-metrics"""
-    if not args.skeleton_metrics:
-        return None
-    return {"max_passes": args.skeleton_max_passes}
-
-
-def print_skeleton(m):
-    print("\t".join(f"{LogColor.RED}{k}{LogColor.RESET}" for k in SKELETON_KEYS))
-    print("\t".join(f"{m[k]:.4f}" for k in SKELETON_KEYS))
-
-
-def object_options(args):
-    """the `objects` argument of the evaluate loops from the flags; None without --object-metrics"""
-    if not args.object_metrics:
-        return None
-    return {"connectivity": args.object_connectivity, "min_area": args.object_min_area}
-
-
-def print_objects(m):
-    print("\t".join(f"{LogColor.RED}{k}{LogColor.RESET}" for k in OBJECT_KEYS))
-    print("\t".join(f"{m[k]:.4f}" for k in OBJECT_KEYS))
-
-
-def curve_accumulator(args):
-    """the `curve` argument of the evaluate loops from the flags; None without --curve-metrics"""
-    if not args.curve_metrics:
-        return None
-    return curve_mod.Accumulator({"bins": args.curve_bins, "threshold": args.threshold})
+def print_keys(m, keys):
+    print("\t".join(f"{LogColor.RED}{k}{LogColor.RESET}" for k in keys))
+    print("\t".join(f"{m[k]:.4f}" for k in keys))
 
 
 def curve_folder(args):
@@ -107,22 +78,23 @@ def curve_folder(args):
     return os.path.dirname(d) if os.path.basename(d) == "weights" else d
 
 
-def report_curve(args, cacc, m):
-    """print the curve keys and write curve.csv and threshold.json"""
-    keys = curve_mod.KEYS + (curve_mod.KEYS_AT if args.threshold is not None else ())
-    print("\t".join(f"{LogColor.RED}{k}{LogColor.RESET}" for k in keys))
-    print("\t".join(f"{m[k]:.4f}" for k in keys))
-    folder = curve_folder(args)
-    os.makedirs(folder, exist_ok=True)
-    curve_mod.write_csv(os.path.join(folder, "curve.csv"), cacc.table())
-    curve_mod.write_threshold(os.path.join(folder, "threshold.json"), m, cacc.K)
+def report(args, ms, m):
+    """print the keys of the families that are on, and with the curve write curve.csv and threshold.json"""
+    for keys in ms.keys:
+        print_keys(m, keys)
+    if ms.curve is not None:
+        folder = curve_folder(args)
+        os.makedirs(folder, exist_ok=True)
+        curve_mod.write_csv(os.path.join(folder, "curve.csv"), ms.curve.table())
+        curve_mod.write_threshold(os.path.join(folder, "threshold.json"), m, ms.curve.K)
+    return m
 
 
 def val(args):
-    boundary = boundary_options(args)
-    skeleton = skeleton_options(args)
-    cacc = curve_accumulator(args)
-    objects = object_options(args)
+    opts = metric_options(args)
+    # the multitask loop below counts into `ms`; evaluate_binary and evaluate build a set of their own from `opts`,
+    # and `ms` then names the keys to print and lends its curve accumulator, whose table is written afterwards
+    ms = MetricSet(**opts)
     num_classes = args.num_classes + 1 if args.task == "multiclass" else 2  # val.py:22-27
     device = torch.device(args.device)
     input_shape = [args.input_size] * 2
@@ -151,38 +123,21 @@ def val(args):
 
     if args.task == "binary":
         m = evaluate_binary(model, loader, device, loss_name=args.loss, pos_weight=None, ignore_index=None,
-                            boundary=boundary, boundary_weight=args.boundary_loss_weight,
-                            boundary_normalize=not args.boundary_loss_pixels, cldice_weight=args.cldice_weight,
-                            cldice_iters=args.cldice_iters, skeleton=skeleton, curve=cacc, objects=objects)
+                            boundary_weight=args.boundary_loss_weight, boundary_normalize=not args.boundary_loss_pixels,
+                            cldice_weight=args.cldice_weight, cldice_iters=args.cldice_iters,
+                            **{**opts, "curve": ms.curve})
         print(f"{LogColor.RED}Dice{LogColor.RESET}\t{LogColor.RED}IoU{LogColor.RESET}\t{LogColor.RED}Precision"
               f"{LogColor.RESET}\t{LogColor.RED}Recall{LogColor.RESET}\t{LogColor.RED}Accuracy{LogColor.RESET}")
         print(f"{m['Dice']:.4f}\t{m['IoU']:.4f}\t{m['Precision']:.4f}\t{m['Recall']:.4f}\t{m['Accuracy']:.4f}")
-        if boundary is not None:
-            print_boundary(m)
-        if skeleton is not None:
-            print_skeleton(m)
-        if cacc is not None:
-            report_curve(args, cacc, m)
-        if objects is not None:
-            print_objects(m)
-        return m
+        return report(args, ms, m)
     if args.task == "multiclass":
         m = evaluate(model, loader, device, dice_loss=True, focal_loss=False, num_classes=num_classes,
-                     lovasz_softmax=args.loss == "lovasz_softmax", boundary=boundary, skeleton=skeleton,
-                     objects=objects)
-        print({k: v for k, v in m.items() if k not in BOUNDARY_KEYS + SKELETON_KEYS + OBJECT_KEYS})
-        if boundary is not None:
-            print_boundary(m)
-        if skeleton is not None:
-            print_skeleton(m)
-        if objects is not None:
-            print_objects(m)
-        return m
+                     lovasz_softmax=args.loss == "lovasz_softmax",
+                     **{k: v for k, v in opts.items() if k != "curve"})  # the curve is of the binary head
+        print({k: v for k, v in m.items() if not any(k in keys for keys in ms.keys)})
+        return report(args, ms, m)
 
     model.eval()
-    bacc = None if boundary is None else BoundaryAccumulator(boundary)
-    sacc = None if skeleton is None else SkeletonAccumulator(skeleton)
-    oacc = None if objects is None else ObjectsAccumulator(objects)
     conf = torch.zeros(4, dtype=torch.int64, device=device)
     per_cls = torch.zeros(3, 2, dtype=torch.int64, device=device)  # [class][correct, count]
     with torch.no_grad():
@@ -190,13 +145,7 @@ def val(args):
             images, seg_t, cls_t = images.to(device), seg_t.to(device), cls_t.to(device)
             seg_logits, cls_logits = model(images)
             losses.binary_confusion(seg_logits, seg_t, conf)
-            if bacc is not None or sacc is not None or oacc is not None:
-                seg_pred = labels_from_logits(seg_logits)
-                for acc_ in (bacc, sacc, oacc):
-                    if acc_ is not None:
-                        acc_.add(seg_pred, seg_t)
-            if cacc is not None:
-                cacc.add(seg_logits, seg_t)
+            ms.add(seg_logits, seg_t)
             pred = cls_logits.argmax(1)
             for c in range(3):
                 sel = cls_t == c
@@ -215,19 +164,8 @@ def val(args):
             print(f"    {name}: {100.0 * c / n:.2f}% ({n} samples)")
     print("=" * 50)
     m = {"IoU": iou, "Dice": dice, "Cls Acc": acc}
-    if bacc is not None:
-        m.update(bacc.metrics())
-        print_boundary(m)
-    if sacc is not None:
-        m.update(sacc.metrics())
-        print_skeleton(m)
-    if cacc is not None:
-        m.update(cacc.metrics())
-        report_curve(args, cacc, m)
-    if oacc is not None:
-        m.update(oacc.metrics())
-        print_objects(m)
-    return m
+    m.update(ms.metrics())
+    return report(args, ms, m)
 
 
 def parse_args(argv=None):
@@ -259,27 +197,7 @@ def parse_args(argv=None):
                    help="pixel tolerance of boundary precision / recall / F1")
     p.add_argument("--boundary-iou-d", default=0, type=int,
                    help="Boundary-IoU band width in pixels; 0 = 2 %% of the image diagonal")
-    p.add_argument("--skeleton-metrics", action="store_true",
-                   help="also report clDice, Skeleton Precision and Skeleton Recall on hard (thinned) skeletons (class "
-                        "1; multiclass: the mean over the classes with a target skeleton)")
-    p.add_argument("--skeleton-max-passes", default=None, type=int,
-                   help="cap of the thinning passes; default min(H, W) // 2 + 8.  An image still losing pixels at the "
-                        "cap is an error, not a silently wrong score")
-    p.add_argument("--object-metrics", action="store_true",
-                   help="also report PQ, SQ, Object F1 / Precision / Recall, Object F1@[.5:.95], Detection Recall, "
-                        "False Object Rate, Split Rate and Merge Rate of the connected components (class 1; multiclass: "
-                        "the mean over the classes with a target object)")
-    p.add_argument("--object-connectivity", default=8, type=int, choices=[4, 8],
-                   help="connectivity of the objects of --object-metrics")
-    p.add_argument("--object-min-area", default=0, type=int,
-                   help="with --object-metrics: drop predicted components below this area first, as predict.py "
-                        "--min-area does")
-    p.add_argument("--curve-metrics", action="store_true",
-                   help="also report the best-IoU threshold with its IoU and F1, IoU at 0.5, AP, AUROC and ECE from a "
-                        "score histogram, and write curve.csv and threshold.json (--task binary and multitask)")
-    p.add_argument("--curve-bins", default=1000, type=int,
-                   help="bins K of the score histogram (even, a multiple of 10, at most 4096); threshold k stands for "
-                        "probability k / K")
+    metric_args.add_metric_args(p)
     p.add_argument("--threshold", default=None, type=float,
                    help="with --curve-metrics: also report IoU / F1 / precision / recall at this probability "
                         "threshold, a multiple of 1 / --curve-bins")
@@ -294,18 +212,8 @@ def parse_args(argv=None):
                    help="the training run's soft-clDice weight, so the reported loss (--task binary) is that objective")
     p.add_argument("--cldice-iters", default=3, type=int, help="levels of the soft skeleton (0 .. 64)")
     args = p.parse_args(argv)
-    if args.skeleton_max_passes is not None and args.skeleton_max_passes < 0:
-        p.error("--skeleton-max-passes must be >= 0")
-    if args.object_min_area < 0:
-        p.error("--object-min-area must be >= 0")
-    if args.curve_metrics:
-        if args.task == "multiclass":
-            p.error("--curve-metrics needs --task binary or multitask (one-vs-rest softmax scores are out of scope)")
-        try:
-            curve_mod.Accumulator({"bins": args.curve_bins, "threshold": args.threshold})
-        except ValueError as e:
-            p.error(f"--curve-bins / --threshold: {e}")
-    elif args.threshold is not None:
+    metric_args.check_metric_args(p, args, metric_options)
+    if args.threshold is not None and not args.curve_metrics:
         p.error("--threshold needs --curve-metrics")
     check_loss_term_args(p, args)
     return args
