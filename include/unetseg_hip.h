@@ -721,6 +721,50 @@ int unetseg_objects_pairs(const int32_t* pred, const int32_t* target, int N, int
 int unetseg_objects_match(const int32_t* pred, const int32_t* target, int N, int H, int W, int c,
                           int64_t* out /* [20], accumulates */, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- vector contours of a class map: crack loops, vertices, signed areas (no reference counterpart;
+ * ---- unetseg_hip/contours.py, predict.py --polygons) --------------------------------------------------
+ * cls int32 [N][H][W], class 0 background, components and roots those of unetseg_ccl_label at `connectivity`.
+ * Pixel (y, x) covers [x, x+1] x [y, y+1].  A crack is a side of a pixel of a non-zero class whose 4-neighbour
+ * across it has another class or lies outside the image; side 0 top (x, y) -> (x+1, y), 1 right, 2 bottom, 3 left,
+ * clockwise on screen with the owner on the right; crack id = (y W + x) 4 + side.  At the head corner, with F the
+ * pixel ahead on the owner's side and D the pixel ahead on the other side ("in" = inside the image and of the
+ * owner's class): connectivity 8: D in -> D's crack (left turn), else F in -> F's (straight on), else the owner's
+ * next side (right turn); connectivity 4: F out -> right turn, else D out -> straight on, else left turn.  The
+ * successor map is a bijection: the cracks fall into closed loops.  A loop's leader is its smallest crack id; it
+ * is the outer loop of its component iff leader == 4 root, else a hole.  A vertex is the tail corner of a crack
+ * whose side differs from its predecessor's.  The stages, on the caller's stream, no block waiting on another:
+ *   unetseg_contours_mask: mask uint8 [N][H][W] (bit s = side s is a crack) and seg int32 [N][H][ceil(W / 64)],
+ *     the cracks of every 64-pixel row segment.  The caller scans seg (exclusive, int64): base, and the total M;
+ *     dense crack indices 0 .. M-1 are in crack-id order.  The other stages share a workspace of
+ *     unetseg_contours_workspace(M) bytes, 16-byte aligned, which scales with M and not with the pixels;
+ *   unetseg_contours_link: off int32 [N][H][W] (the dense index of each pixel's first crack) and, per crack, its
+ *     id in the flat batch, its successor and whether its tail is a vertex;
+ *   unetseg_contours_rank: pointer doubling, 2 R + 2 launches with R = ceil(log2 M) rounded up to even: the leader
+ *     of every crack, then the cracks, vertices and doubled shoelace area (64-bit) from every crack to the end of
+ *     its loop cut before the leader; a leader holds its loop's totals;
+ *   unetseg_contours_emit: the rows (image, class, root, hole, first, count, area, cracks) of the loops led by
+ *     `leaders` (the caller orders them by (image, root, leader) and scans their vertex counts into `first`) and
+ *     the vertices (x, y) of loop i at first[i] onward, in travel order from the first vertex at or after the
+ *     leader's tail.  area = the signed shoelace area (> 0 outer, < 0 hole), cracks = the loop's length.
+ * All integer and a function of the input only.  Checked before any launch: null pointers, N, H, W >= 0,
+ * H W <= 2^29 (no id, count or area leaves int32), connectivity 4 or 8, 1 <= M <= 2^31 - 1, ws_bytes and the
+ * alignment of ws.  An empty batch launches nothing and returns 0.  The failure word counts successors that were
+ * no crack (0 unless there is a bug; such a crack becomes its own successor, so nothing is read out of bounds). */
+/* host only: the mask kernel holds a tile of *tw x *th pixels and its halo in LDS */
+int unetseg_contours_tile(int* tw, int* th);
+size_t unetseg_contours_workspace(long M); /* host only; 0 for a refused M */
+/* host only: at[0 .. 7) = byte offsets in the workspace of the crack ids int64 [M] ((n H W + y W + x) 4 + side),
+ * successors, vertex flags and leaders int32 [M], and rank's cracks int32 [M], vertices int32 [M] and doubled
+ * areas int64 [M]; at[7] = the failure word uint32 */
+int unetseg_contours_layout(long M, int64_t* at /* [8] */);
+int unetseg_contours_mask(const int32_t* cls, int N, int H, int W, uint8_t* mask, int32_t* seg, void* stream);
+int unetseg_contours_link(const int32_t* cls, const uint8_t* mask, const int64_t* base, int N, int H, int W,
+                          int connectivity, long M, int32_t* off, void* ws, size_t ws_bytes, void* stream);
+int unetseg_contours_rank(int N, int H, int W, long M, void* ws, size_t ws_bytes, void* stream);
+int unetseg_contours_emit(const int32_t* cls, const int32_t* root, int N, int H, int W, long M,
+                          const int32_t* leaders, const int32_t* first, int L, int32_t* loops /* [L][8] */,
+                          int32_t* vertices /* [V][2] */, long V, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- device augmentation of the loader (utils/hf_dataloader.py:67-105, 111-180, 183-213) -------
  * Replaces HFUnetDataset.get_random_data + preprocess + hf_unet_dataset_collate for one batch:
  * PIL BICUBIC image / NEAREST mask resize (bit-exact), flip, paste on the grey / zero canvas,

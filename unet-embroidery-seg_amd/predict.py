@@ -33,6 +33,16 @@ unetseg_hip/skeleton.py: Guo-Hall thinning per class) and writes the centerlines
 beside the mask, in the class colours on black; with ``--components`` every entry of the component list
 gains ``skeleton_px``, the number of skeleton pixels of that component.  Off by default: nothing is launched
 and the other outputs stay byte for byte what they were.
+
+``--polygons`` (no reference counterpart) traces the outlines of the cleaned label map on the device
+(csrc/contours.hip, unetseg_hip/contours.py: crack following by parallel list ranking) and writes ``<name>.json``
+beside the mask, a labelme document in the reference's own annotation format (labelme_converter.py reads such
+files): one polygon per component, then one ``_background_`` polygon per hole (and once more, as one exact keyhole
+polygon at the end, each component of an 8-connected class that crosses a later one at a saddle), simplified
+with closed-loop Douglas-Peucker at ``--polygon-epsilon`` pixels (default 1.0; 0 keeps the exact pixel outline) and labelled
+from ``--class-names a,b,c`` (class 0 first) or ``class_<c>``.  With ``--components`` every entry of the component
+list gains ``perimeter``, the length of the component's outlines in pixel sides.  Off by default: nothing is
+launched and the other outputs stay byte for byte what they were.
 """
 from __future__ import annotations
 
@@ -53,7 +63,7 @@ import torch  # noqa: E402
 from PIL import Image  # noqa: E402
 
 from model.model_factory import SUPPORTED_MODELS, build_model  # noqa: E402
-from unetseg_hip import ccl, skeleton as skel  # noqa: E402
+from unetseg_hip import ccl, contours, skeleton as skel  # noqa: E402
 from unetseg_hip.lib import lib  # noqa: E402
 from unetseg_hip.tta import MODES as TTA_MODES, TTA  # noqa: E402
 from utils import tiling  # noqa: E402
@@ -102,30 +112,39 @@ def letterbox(image, device):
     return x, nw, nh
 
 
-def finish_labels(labels, min_area=0, max_hole=0, connectivity=8, components=False, skeleton=False):
+def finish_labels(labels, min_area=0, max_hole=0, connectivity=8, components=False, skeleton=False,
+                  polygons=False):
     """the device label map cleaned (unetseg_hip.ccl.clean) and downloaded; with ``components`` also the
     cleaned map's component table int32 [K][7], (image, class, area, ymin, xmin, ymax, xmax); with
     ``skeleton`` the cleaned map is thinned on the device (unetseg_hip.skeleton.thin) and the skeleton map
-    int32 [H][W] comes last, and the table has an eighth column, the component's skeleton pixels"""
+    int32 [H][W] follows, and the table has an eighth column, the component's skeleton pixels; with
+    ``polygons`` the cleaned map's outlines are traced on the device (unetseg_hip.contours.trace) and the
+    component list of ``contours.polygons`` comes last"""
     labels = ccl.clean(labels, min_area, max_hole, connectivity)
-    if not skeleton:
+    if not (skeleton or polygons):
         if components:
             return labels.cpu().numpy(), ccl.components(labels, connectivity).cpu().numpy()
         return labels.cpu().numpy()
-    sk, unconverged = skel.thin(labels, return_unconverged=True)
+    sk = unconverged = None
+    if skeleton:
+        sk, unconverged = skel.thin(labels, return_unconverged=True)
     done = (labels.cpu().numpy(),)
     if components:
         done += (ccl.components(labels, connectivity, skeleton=sk).cpu().numpy(),)
-    done += (sk.cpu().numpy(),)
-    if int(unconverged.sum().item()):  # read after the downloads above: no extra wait
+    if skeleton:
+        done += (sk.cpu().numpy(),)
+    if polygons:
+        done += (contours.polygons(*contours.trace(labels, connectivity)),)
+    if skeleton and int(unconverged.sum().item()):  # read after the downloads above: no extra wait
         raise RuntimeError(f"thinning had not converged after {skel.default_max_passes(*labels.shape[-2:])} passes")
     return done
 
 
-def predict_labels(model, image, device, min_area=0, max_hole=0, connectivity=8, components=False, skeleton=False):
+def predict_labels(model, image, device, min_area=0, max_hole=0, connectivity=8, components=False, skeleton=False,
+                   polygons=False):
     """predict.py:72-93: the argmax label map int32 [H][W] at the image's original size, cleaned as
-    ``finish_labels`` says (and followed by the component table when ``components`` is set, and by the
-    skeleton map when ``skeleton`` is)"""
+    ``finish_labels`` says (and followed by the component table when ``components`` is set, by the
+    skeleton map when ``skeleton`` is, and by the polygon list when ``polygons`` is)"""
     x, nw, nh = letterbox(image, device)
     with torch.no_grad():
         pr = model(x)[0].float().contiguous()
@@ -134,17 +153,18 @@ def predict_labels(model, image, device, min_area=0, max_hole=0, connectivity=8,
     labels = torch.empty(oh, ow, dtype=torch.int32, device=device)
     lib.softmax_resize_argmax(pr.data_ptr(), C, H, W, (INPUT_SHAPE[0] - nh) // 2, (INPUT_SHAPE[1] - nw) // 2, nh, nw,
                               oh, ow, labels.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
-    return finish_labels(labels, min_area, max_hole, connectivity, components, skeleton)
+    return finish_labels(labels, min_area, max_hole, connectivity, components, skeleton, polygons)
 
 
 def predict_labels_tiled(model, image, device, tile=512, overlap=64, tile_batch=8, bf16=False, return_probs=False,
-                         min_area=0, max_hole=0, connectivity=8, components=False, skeleton=False):
+                         min_area=0, max_hole=0, connectivity=8, components=False, skeleton=False, polygons=False):
     """the argmax label map int32 [H][W] of the image at its native resolution: overlapping tiles
     (utils/tiling.py) gathered on the device, ``model`` (any callable [B,3,t,t] fp32 -> [B,C,t,t]
     logits, C >= 2) run over ranges of ``tile_batch`` tiles, the window-weighted softmax of every tile
     accumulated in ascending tile order and normalised, the label map cleaned as ``finish_labels`` says.
     With ``return_probs`` also the blended fp32 probabilities [C][H][W] (of the map before cleaning);
-    with ``components`` the component table comes after those, and with ``skeleton`` the skeleton map last."""
+    with ``components`` the component table comes after those, with ``skeleton`` the skeleton map, and with
+    ``polygons`` the polygon list last."""
     tiling.check(tile, overlap)
     rgb = np.array(image, np.uint8)  # a writable C-contiguous copy (a PIL image's buffer is read-only)
     if rgb.ndim != 3 or rgb.shape[2] != 3:
@@ -174,9 +194,9 @@ def predict_labels_tiled(model, image, device, tile=512, overlap=64, tile_batch=
     probs = torch.empty_like(acc) if return_probs else None
     lib.tile_finish(acc.data_ptr(), acc.shape[0], H, W, tile, overlap, probs.data_ptr() if return_probs else None,
                     labels.data_ptr(), st)
-    done = finish_labels(labels, min_area, max_hole, connectivity, components, skeleton)
+    done = finish_labels(labels, min_area, max_hole, connectivity, components, skeleton, polygons)
     if return_probs:
-        if components or skeleton:
+        if components or skeleton or polygons:
             return (done[0], probs.cpu().numpy()) + tuple(done[1:])
         return done, probs.cpu().numpy()
     return done
@@ -205,11 +225,40 @@ def check_clean(min_area, max_hole, connectivity):
         raise ValueError(f"--connectivity must be 4 or 8, got {connectivity}")
 
 
-def components_json(table):
+def check_polygons(epsilon, class_names, num_classes):
+    """the command line's polygon options: epsilon >= 0; at most one name per class, class 0 included"""
+    if epsilon < 0:
+        raise ValueError(f"--polygon-epsilon must not be negative, got {epsilon}")
+    if class_names is not None and len(class_names) > num_classes:
+        raise ValueError(f"--class-names gives {len(class_names)} names for {num_classes} classes (class 0 included)")
+
+
+def parse_class_names(text):
+    """``a,b,c`` -> ["a", "b", "c"] (class 0 first); None or empty -> None"""
+    if not text:
+        return None
+    return [t.strip() for t in text.split(",")]
+
+
+def components_json(table, polys=None):
     """the component table as the list ``--components`` writes: class, area, bbox [x0, y0, x1, y1], in table order;
-    a table with the skeleton column adds skeleton_px"""
+    a table with the skeleton column adds skeleton_px, and the polygon list (``contours.polygons`` of the same map
+    and connectivity: the same components in the same order) adds perimeter"""
+    if polys is not None and len(polys) != len(table):
+        raise ValueError(f"{len(polys)} polygons for {len(table)} components")
     return [dict({"class": int(r[1]), "area": int(r[2]), "bbox": [int(r[4]), int(r[3]), int(r[6]), int(r[5])]},
-                 **({"skeleton_px": int(r[7])} if len(r) > 7 else {})) for r in table]
+                 **({"skeleton_px": int(r[7])} if len(r) > 7 else {}),
+                 **({"perimeter": int(polys[k]["perimeter"])} if polys is not None else {}))
+            for k, r in enumerate(table)]
+
+
+def polygons_json(polys, height, width, image_path, class_names=None, epsilon=1.0):
+    """the labelme document ``--polygons`` writes (``contours.labelme``); a class without a name is ``class_<c>``"""
+    names = None
+    if class_names is not None:
+        top = max([p["class"] for p in polys], default=0)
+        names = list(class_names) + [f"class_{c}" for c in range(len(class_names), top + 1)]
+    return contours.labelme(polys, height, width, image_path, names, epsilon)
 
 
 def blend(old, seg, alpha=0.7):
@@ -220,10 +269,11 @@ def blend(old, seg, alpha=0.7):
 
 
 def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, device=None, tile=0, overlap=64,
-                 tile_batch=8, bf16=False, min_area=0, max_hole=0, connectivity=8, components=False, skeleton=False):
+                 tile_batch=8, bf16=False, min_area=0, max_hole=0, connectivity=8, components=False, skeleton=False,
+                 polygons=False, polygon_epsilon=1.0, class_names=None):
     """predict.py:41-109; tile > 0 takes the label map from predict_labels_tiled; ``components`` writes
     the cleaned map's component list to ``<name>_components.json`` beside the mask, ``skeleton`` the cleaned
-    map's centerlines to ``<name>_skeleton.png``"""
+    map's centerlines to ``<name>_skeleton.png``, ``polygons`` its outlines to ``<name>.json`` (labelme)"""
     try:
         image = Image.open(file_path)
     except (FileNotFoundError, IOError) as e:
@@ -234,7 +284,7 @@ def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, devic
     old_img = image.copy()
     # only the cleanup options that are set: without any, the two calls are what they were before cleanup existed
     post = {k: v for k, v in (("min_area", min_area), ("max_hole", max_hole), ("components", components),
-                                  ("skeleton", skeleton)) if v}
+                                  ("skeleton", skeleton), ("polygons", polygons)) if v}
     if post:
         post["connectivity"] = connectivity
     if tile:
@@ -242,6 +292,10 @@ def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, devic
                                   **post)
     else:
         pr = predict_labels(model, image, device, **post)
+    polys = None
+    if polygons:
+        pr, polys = pr[:-1], pr[-1]
+        pr = pr[0] if len(pr) == 1 else pr
     if skeleton:
         table, sk_map = pr[1] if components else None, pr[-1]
         pr = pr[0]
@@ -255,11 +309,14 @@ def detect_image(file_path, model, num_classes, exp_folder, mix_type=True, devic
     print(f"Mask saved at: {save_path}")
     if components:
         with open(save_path[:-len("_mask.png")] + "_components.json", "w") as f:
-            json.dump(components_json(table), f)
+            json.dump(components_json(table, polys), f)
     if skeleton:
         palette = np.array(colors_for(num_classes), np.uint8)
         palette[0] = 0  # the background stays black whatever the palette
         Image.fromarray(palette[sk_map]).save(save_path[:-len("_mask.png")] + "_skeleton.png")
+    if polygons:
+        with open(save_path[:-len("_mask.png")] + ".json", "w") as f:
+            json.dump(polygons_json(polys, oh, ow, os.path.basename(file_path), class_names, polygon_epsilon), f)
     return save_path
 
 
@@ -279,8 +336,10 @@ def predict(args):
     """predict.py:112-145"""
     check_tiling(args.tile, args.overlap, args.tile_batch)
     check_clean(args.min_area, args.max_hole, args.connectivity)
-    exp_folder = create_val_exp_folder(args.out_dir)
     num_classes = args.num_classes + 1
+    class_names = parse_class_names(args.class_names)
+    check_polygons(args.polygon_epsilon, class_names, num_classes)
+    exp_folder = create_val_exp_folder(args.out_dir)
     assert os.path.exists(args.weights), f"weights {args.weights} not found."
     if not torch.cuda.is_available():
         raise RuntimeError("the HIP inference path needs a GPU (no CPU fallback)")
@@ -298,7 +357,8 @@ def predict(args):
     saved = [detect_image(f, model, num_classes, exp_folder, mix_type=args.mix_type, device=device, tile=args.tile,
                           overlap=args.overlap, tile_batch=args.tile_batch, bf16=args.bf16, min_area=args.min_area,
                           max_hole=args.max_hole, connectivity=args.connectivity, components=args.components,
-                          skeleton=args.skeleton)
+                          skeleton=args.skeleton, polygons=args.polygons, polygon_epsilon=args.polygon_epsilon,
+                          class_names=class_names)
              for f in files if f.endswith((".jpg", ".png", ".jpeg"))]
     print(f"inference time for: {time_synchronized() - t0}")
     return saved
@@ -334,6 +394,14 @@ def parse_args(argv=None):
     p.add_argument("--skeleton", action="store_true",
                    help="also write <name>_skeleton.png: the centerlines (Guo-Hall thinning) of the cleaned label map in "
                         "the class colours on black; with --components the list gains skeleton_px per component")
+    p.add_argument("--polygons", action="store_true",
+                   help="also write <name>.json: the outlines of the cleaned label map as a labelme document, one "
+                        "polygon per component and one _background_ polygon per hole; with --components the list "
+                        "gains perimeter per component")
+    p.add_argument("--polygon-epsilon", default=1.0, type=float,
+                   help="Douglas-Peucker tolerance of --polygons in pixels (0: the exact pixel outline)")
+    p.add_argument("--class-names", default=None,
+                   help="comma-separated labels of --polygons, class 0 first (default: class_<c>)")
     return p.parse_args(argv)
 
 

@@ -161,6 +161,13 @@ SIGNATURES = {
     "unetseg_objects_label": (I, [P, P, I, I, I, I, P, SZ, P]),
     "unetseg_objects_pairs": (I, [P, P, I, I, I, I, I, P, SZ, P]),
     "unetseg_objects_match": (I, [P, P, I, I, I, I, P, P, SZ, P]),
+    "unetseg_contours_tile": (I, [P, P]),
+    "unetseg_contours_workspace": (SZ, [L]),
+    "unetseg_contours_layout": (I, [L, P]),
+    "unetseg_contours_mask": (I, [P, I, I, I, P, P, P]),
+    "unetseg_contours_link": (I, [P, P, P, I, I, I, I, L, P, P, SZ, P]),
+    "unetseg_contours_rank": (I, [I, I, I, L, P, SZ, P]),
+    "unetseg_contours_emit": (I, [P, P, I, I, I, L, P, P, I, P, P, L, P, SZ, P]),
     "unetseg_adam_ema": (I, [P, P, P, P, P, L, F, F, F, F, F, I, F, P, P]),
     "unetseg_adam_ema_dev": (I, [P, P, P, P, P, L, P, P, F, F, F, F, F, I, P, P]),
     "unetseg_swap_f32": (I, [P, P, L, P]),
